@@ -16,9 +16,17 @@ rank per step, like the reference's DistributedSampler partitioning).
 any GPU call, runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same flags>` as a child
 process, relays its output (rank 0's JSON line) and exits with its code.  Nothing is ever re-exec'ed.
 
-Prints ONE JSON line on rank 0, with `roofline` (bf16 MFMA GEMM family, measured with HIP events around every GEMM
-launch of the LAST warm-up step -- an extra untimed step only with --warmup 0) and `cpu_baseline` (the CPU oracle timed
-on this box's host cores on a bounded sample).  A progress line per step goes to stderr.
+Prints ONE JSON line on rank 0.  A plain run sets up, runs the W warm-up and K timed steps and prints the line; its
+`roofline`, `cpu_baseline` and `vae_decode` fields are null.  With `--full` the run also measures them: `roofline` (bf16
+MFMA GEMM family, measured with HIP events around every GEMM launch of the LAST warm-up step -- an extra untimed step only
+with --warmup 0), `cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample) and `vae_decode` (a
+side measurement after the timed region).  A progress line per step goes to stderr.
+
+`--dump-outputs DIR` writes, after the timed steps, what the LAST timed step computed as float32 / float64 `.npy` files
+(rank 0): the values `train_one_step` returns (loss, grad_norm, policy_loss, kl_loss, clip_frac, per-head reward means)
+and a fixed, seeded sample of 2^20 positions of the flat fp32 master weights after the step, of that step's update to
+them and of the AdamW moments (16 MiB in all).  Every input is seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -85,20 +93,33 @@ def main():
                          "leftover chunk): at 4 the FF pre-activations AND the QKV outputs of all 57 blocks fit in HBM beside the "
                          "optimizer state, so the recompute pass runs no GEMM at all (flux_backward.KEEP_FF / KEEP_QKV); same "
                          "box, round 4: 18.45 s per step against 18.72 s at 7 (7+5 / 7+1, 18 blocks kept)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vae", action="store_true", help="skip the VAE-decode side measurement (reported beside the metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline of the GEMM family, the CPU baseline and the VAE-decode side measurement "
+                         "(off by default: a plain run times the train steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-vae", action="store_true",
+                    help="with --full: skip the VAE-decode side measurement (reported beside the metric)")
     ap.add_argument("--skip-dead-backward", action="store_true",
                     help="do not execute the backward passes of the G %% accum leftover samples, whose gradients the "
                          "reference computes and discards (identical outputs; NOT the default, NOT the headline number)")
     ap.add_argument("--attention", default="bf16", choices=["bf16", "fp8"],
                     help="attention forward dtype; fp8 = the e4m3 MFMA path of BASELINE.json configs[4] (NOT the headline "
                          "configuration: the line's dtype then reads bf16+fp8attn)")
-    ap.add_argument("--gemm-shapes", default=None, help="write the per-shape GEMM time table of the roofline step here")
+    ap.add_argument("--gemm-shapes", default=None,
+                    help="with --full: write the per-shape GEMM time table of the roofline step here")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0,
                     help="wall-time budget of the CPU-baseline sample (it stops widening the sample once this is used up)")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:                  # a plain run: set-up, warm-up, the timed steps, outputs, the line -- nothing else
+        a.no_roofline = a.no_cpu_baseline = a.no_vae = True
+    if a.gemm_shapes and a.no_roofline:
+        ap.error("--gemm-shapes needs the roofline step (--full, without --no-roofline)")
 
     if a.cpu_baseline_child:        # (internal) the CPU-baseline sample as its own process: no GPU call, one JSON line
         print("CPU_BASELINE " + json.dumps(_cpu_baseline_measure(a.cpu_baseline_seconds)), flush=True)
@@ -251,12 +272,16 @@ def main():
         except Exception:  # noqa: BLE001 - a failed sample falls back to the in-process measurement after the timed region
             cpu_child.kill()
             cpu_measured = None
+    dump_idx = _dump_index(model.store.numel, dev) if a.dump_outputs and rank == 0 else None
+    w_before = None
     fence()
     ms0 = torch.cuda.memory_stats()
     step_s = []
     t0 = time.perf_counter()
     for i in range(a.steps):
         t1 = time.perf_counter()
+        if dump_idx is not None and i == a.steps - 1:      # one 2^20-element gather, queued without a sync
+            w_before = model.store.w32.index_select(0, dump_idx)
         last = one_step()
         step_s.append(time.perf_counter() - t1)
         if rank == 0 and (i + 1) % 2 == 0:  # a progress line every other step, from host time only (no device sync)
@@ -264,6 +289,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     ms1 = torch.cuda.memory_stats()
+    if dump_idx is not None:
+        _dump_outputs(a.dump_outputs, last[0], model, opt, dump_idx, w_before)
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -418,6 +445,41 @@ def _vae_decode_side_measurement(dev, args, G):
 def _lib_version():
     from mixgrpo_amd import _lib
     return int(_lib.lib().mgx_version())
+
+
+DUMP_SAMPLE = 1 << 20               # positions of the flat parameter vector sampled by --dump-outputs
+DUMP_SEED = 0
+
+
+def _dump_index(numel, dev):
+    """The fixed, seeded sample of flat parameter positions that --dump-outputs writes (sorted: one coalesced gather)."""
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    return torch.randint(numel, (DUMP_SAMPLE,), generator=g).sort().values.to(dev)
+
+
+def _dump_outputs(out_dir, res, model, opt, idx, w_before):
+    """What the last timed step computed, as DIR/<name>.npy: the values train_one_step returns (float64) and the sampled
+    master weights after the step, the step's update to them and the AdamW moments (float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    loss, grad_norm, policy_loss, kl_loss, clip_frac, rewards = res
+    arrays = {"loss": loss, "policy_loss": policy_loss, "kl_loss": kl_loss, "clip_frac": clip_frac}
+    if grad_norm is not None:       # None only when the step ran no optimizer update (G < gradient_accumulation_steps)
+        arrays["grad_norm"] = grad_norm
+    if isinstance(rewards, dict):
+        arrays.update({f"reward_{h}": r for h, r in rewards.items()})
+    else:
+        arrays["reward"] = rewards
+    arrays = {k: np.asarray([v], dtype=np.float64) for k, v in arrays.items()}
+    w_after = model.store.w32.index_select(0, idx)
+    arrays["weights_sample"] = w_after
+    arrays["weight_update_sample"] = w_after - w_before
+    arrays["adam_m_sample"] = opt.m.index_select(0, idx)
+    arrays["adam_v_sample"] = opt.v.index_select(0, idx)
+    for k, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
 
 
 def _self_launch(n):

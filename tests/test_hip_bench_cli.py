@@ -1,5 +1,6 @@
-"""bench.py end to end on the small stand-in workload: the one-GPU line carries the contract's fields (roofline,
-cpu_baseline), and the N = 2 launch (the driver's `python -m torch.distributed.run ... bench.py --gpus 2` form, here with
+"""bench.py end to end on the small stand-in workload: the one-GPU `--full` line carries the contract's fields (roofline,
+cpu_baseline), a plain run measures nothing but the steps and writes the last step's outputs with --dump-outputs, and
+the N = 2 launch (the driver's `python -m torch.distributed.run ... bench.py --gpus 2` form, here with
 both ranks on cuda:0 over gloo) runs its collectives to completion and reports the whole-job rate.  Guards the
 distributed path of the bench against rank-asymmetric code (a rank-0-only train step deadlocks the gradient all-reduce)."""
 import json
@@ -24,8 +25,8 @@ def _line(out):
 
 
 def test_bench_one_gpu_line_has_the_contract_fields():
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "tiny_256_T8_W2_G4", "--steps", "2", "--warmup", "1"],
-                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "tiny_256_T8_W2_G4", "--steps", "2", "--warmup", "1",
+                        "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _line(r.stdout)
     assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0
@@ -41,12 +42,32 @@ def test_bench_one_gpu_line_has_the_contract_fields():
     assert vd["ms_per_image"] > 0 and "not part of `value`" in vd["note"]
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """Without --full the line leaves the side measurements out; --dump-outputs writes what the last timed step computed:
+    the returned values (float64) and the seeded samples of weights, update and AdamW moments (float32), 64 MB at most."""
+    import numpy as np
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "tiny_256_T8_W2_G4", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = _line(r.stdout)
+    assert j["steps"] == 3 and len(j["host_s_per_timed_step"]) == 3 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 4 / (j["ms_per_step"] / 1e3)) / j["value"] < 1e-3
+    assert j["roofline"] is None and j["cpu_baseline"] is None and j["vae_decode"] is None
+    files = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    assert {"loss", "grad_norm", "clip_frac", "weights_sample", "weight_update_sample", "adam_m_sample"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(f.stat().st_size for f in out.glob("*.npy")) <= 64 * 2 ** 20
+    assert files["loss"][0] == j["last_step"]["loss"] and files["grad_norm"][0] == j["last_step"]["grad_norm"]
+    assert np.isfinite(files["weights_sample"]).all() and np.abs(files["weight_update_sample"]).max() > 0
+
+
 def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, MGX_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = free_port()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-                        "--workload", "tiny_256_T8_W2_G4", "--steps", "2", "--warmup", "1"],
+                        "--workload", "tiny_256_T8_W2_G4", "--steps", "2", "--warmup", "1", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _line(r.stdout)
@@ -79,7 +100,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MGX_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--workload", "tiny_256_T8_W2_G4", "--steps", "1",
-                        "--warmup", "1", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _line(r.stdout)
     assert j["n_gpus"] == 2 and j["config"]["parallelism"] == "dp2" and j["config"]["global_batch"] == 8

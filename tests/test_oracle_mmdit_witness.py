@@ -72,9 +72,17 @@ def test_rotation(tag):
 
 
 def test_sinusoid():
-    out = OM.sincos256(T_["sincos/t"])
+    t = T_["sincos/t"]
+    out = OM.sincos256(t)
     assert out.shape == (9, 256)
-    eq(out, T_["sincos/out"])
+    if EXACT:
+        eq(out, T_["sincos/out"])
+    else:
+        # off the fixture host the vector exp behind the frequencies may round differently in the last bit: the angle
+        # t * freq (up to 3500 rad here) then moves by up to an ulp of itself, and cos / sin with it
+        ang = (t[:, None].abs() * torch.exp(-math.log(10000) * torch.arange(128) / 128)).repeat(1, 2)
+        err = (out - T_["sincos/out"]).abs()
+        assert (err <= 2e-6 + 2 * torch.finfo(torch.float32).eps * ang).all(), err.max()
     # [cos | sin] order (flip_sin_to_cos=True) and frequency 0 is exp(0) = 1: column 0 = cos(t), column 128 = sin(t)
     assert torch.allclose(out[:, 0], torch.cos(T_["sincos/t"])) and torch.allclose(out[:, 128], torch.sin(T_["sincos/t"]))
     assert out[5].tolist() == [1.0] * 128 + [0.0] * 128             # t = 0

@@ -15,8 +15,14 @@ T_, M_ = load_golden("rollout")
 EXACT = host_matches_fixture_host()
 
 
-def eq(a, b):
-    assert_same(a, b, exact=EXACT)
+def eq(a, b, tag=""):
+    kw = {}
+    if not EXACT and tag.startswith("dpmall"):
+        # Off the fixture host, CPU vector math and GEMM kernels may round differently in the last bit.  The second-order
+        # DPM-Solver++ steps extrapolate from the difference of two model outputs: a one-ulp difference of the latents
+        # (first seen at step 5 of 8) grows to ~40 ulp of their largest element by the end.  Held to 2e-5 of that element.
+        kw = dict(rtol=0.0, atol=2e-5 * b.abs().max().item())
+    assert_same(a, b, exact=EXACT, **kw)
 
 
 @pytest.mark.parametrize("inject", [False, True])
@@ -38,9 +44,9 @@ def test_rollout(case, inject):
         z, lat, all_lat, all_lp = R.run_sample_step(a, T_["in/z0"], range(T), sig, model, T_["in/ehs"], T_["in/pooled"],
                                                     T_["in/text_ids"], T_["in/img_ids"], True, det, noises=noises)
     assert all_lp.shape[1] == case["steps_run"]
-    eq(z, T_[f"{tag}/z"])
-    eq(lat, T_[f"{tag}/latents"])
-    eq(all_lat, T_[f"{tag}/all_latents"])
+    eq(z, T_[f"{tag}/z"], tag)
+    eq(lat, T_[f"{tag}/latents"], tag)
+    eq(all_lat, T_[f"{tag}/all_latents"], tag)
     eq(all_lp, T_[f"{tag}/all_log_probs"])
 
 
