@@ -212,7 +212,8 @@ int mgx_transpose_bf16(const uint16_t* in, uint16_t* out, float* colsum_partial,
 int mgx_ln_modulate_fwd(const uint16_t* x, long ldx, long x_rpb, long x_bstride, const uint16_t* shift,
                         const uint16_t* scale, long mod_ld, uint16_t* y, long ldy, float* stats, long M, int D,
                         void* stream);
-/* Backward of the above: dx (+)= dLN, dshift/dscale (bf16, [B, mod_ld] chunks) = per-batch column sums. */
+/* Backward of the above: dx = bf16(dLN), or with `accumulate` dx = bf16(dx + dLN) (ONE rounding of the fp32 sum of the old
+ * bf16 value and dLN); dshift/dscale (bf16, [B, mod_ld] chunks) are written (not accumulated) with per-batch column sums. */
 long mgx_ln_modulate_bwd_workspace(long M, long rpb, int D);
 int mgx_ln_modulate_bwd(const uint16_t* dy, long lddy, const uint16_t* x, long ldx, long x_rpb, long x_bstride,
                         const uint16_t* scale, long mod_ld, uint16_t* dx, long lddx, long dx_rpb, long dx_bstride,

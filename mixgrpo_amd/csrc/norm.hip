@@ -83,8 +83,9 @@ __global__ void __launch_bounds__(256) ln_mod_fwd_kernel(const bf16_raw* __restr
 }
 
 // ------------------------------------------------------------------------------------- LN-modulate backward
-// dy [M, D] -> dx accumulated into the residual-stream gradient (row-batched, bf16), and per-batch column sums
-// dshift[b, :] += sum_rows dy, dscale[b, :] += sum_rows dy * xhat (two-stage, deterministic).
+// dy [M, D] -> dx (row-batched, bf16): bf16(dLN), or with `accumulate` bf16(old + dLN) -- one rounding of the fp32 sum -- into
+// the residual-stream gradient; and per-batch column sums dshift[b, :] = sum_rows dy, dscale[b, :] = sum_rows dy * xhat, written
+// (not accumulated) as bf16 (two-stage, deterministic).
 // Each block owns ROWS_PER_BLOCK consecutive rows of ONE batch; each wave walks rows w, w+4, ...
 constexpr int LN_BWD_ROWS = 32;
 template <int NV>
@@ -201,7 +202,8 @@ __global__ void __launch_bounds__(256) ln_mod_bwd_kernel(const bf16_raw* __restr
   for (int c = threadIdx.x; c < 2 * D; c += 256) part[(long)blockIdx.x * 2 * D + c] = red[c];
 }
 
-// dshift[b, c] (+)= sum over the batch's blocks; gradients are bf16 [B, mod_ld] chunks of the modulation vector.
+// dshift[b, c] = bf16(sum over the batch's blocks) (written, not accumulated); gradients are bf16 [B, mod_ld] chunks of the
+// modulation vector.
 // Block = 64 columns x 4 lanes over the blocks (a thread per column walking all partials alone is latency-bound).
 __global__ void __launch_bounds__(256) ln_mod_bwd_finish_kernel(const float* __restrict__ part, bf16_raw* __restrict__ dshift,
                                                                 bf16_raw* __restrict__ dscale, long mod_ld, int D,

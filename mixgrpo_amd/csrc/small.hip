@@ -215,7 +215,7 @@ __global__ void cast_bf16_f32_kernel(const bf16_raw* __restrict__ x, float* __re
 
 // gate-residual backward helpers on [rows, D] row-batched streams:
 //   dgate[b, c] = sum_rows dout[m, c] * y[m, c]   (y = pre-gate branch output), dy[m, c] = bf16(gate[b, c] * dout[m, c])
-// Block = 32 rows of one batch x 256 columns... each thread owns 1 column pair across the block's rows.
+// Block = GR_ROWS rows of one batch x 512 columns: each thread owns one column pair across the block's rows.
 constexpr int GR_ROWS = 64;
 __global__ void __launch_bounds__(256) gate_bwd_kernel(const bf16_raw* __restrict__ dout, long ldd, long d_rpb,
                                                        long d_bstride, const bf16_raw* __restrict__ y, long ldy,

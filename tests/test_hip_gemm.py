@@ -488,13 +488,17 @@ def test_linear_t_declines_what_the_persistent_kernel_cannot_take():
 
 
 @pytest.mark.parametrize("B,rows,H,K,s0,S", [(8, 512, 24, 1024, 0, 4608), (4, 2176, 4, 512, 128, 2432), (6, 1280, 6, 256, 0, 1280),
-                                             (1, 4736, 8, 320, 64, 4800)])
+                                             (1, 4736, 8, 320, 64, 4800), (8, 4096, 24, 3072, 512, 4608),
+                                             (5, 4224, 24, 256, 128, 4352)])
 @pytest.mark.parametrize("q_scale,paired", [(1.0, False), (1.4426950408889634 / 128 ** 0.5, False), (1.4426950408889634 / 128 ** 0.5, True)])
 def test_linear_qk_norm_rope_equals_projection_then_norm_pass(B, rows, H, K, s0, S, q_scale, paired):
     """mgx_linear_qk_norm_rope (RMSNorm + RoPE + head split in the q | k projection's epilogue: sums of squares crossing two
     waves through LDS, the K-loop's early / late barrier protocol kept) against mgx_gemm_bf16 + mgx_qk_norm_rope_fwd_qs on the
     same operands: the epilogue restates that kernel's arithmetic in its summation order, so Q and K are equal BIT FOR BIT;
-    positions outside s0 .. s0 + rows stay untouched.  (4736 rows: the last tile row is half outside the matrix.)"""
+    positions outside s0 .. s0 + rows stay untouched.  (4736 rows: the last tile row is half outside the matrix.  8 x 4096 rows,
+    K 3072: the rollout's image-stream projection, 3072 tiles = 12 per workgroup.  5 x 4224 rows: M % 256 == 128 -- the last
+    tile row half outside -- and 1992 tiles, ~8 per workgroup.)  A second launch gives the same bits: the epilogue's sums
+    reuse an A stage of the K-loop, and a race on that stage would show as a run-to-run difference."""
     from mixgrpo_amd import ops
     from mixgrpo_amd.ops import Rows
     g = torch.Generator().manual_seed(B * 7 + rows + H + K)
@@ -517,6 +521,11 @@ def test_linear_qk_norm_rope_equals_projection_then_norm_pass(B, rows, H, K, s0,
     K1 = torch.full_like(Q1, 7.0)
     assert ops.linear_qk_norm_rope(X, W[:2 * d], bias[:2 * d], wq, wk, cos, sin, Q1, K1, B, H, S, rows, s0, K, q_scale=q_scale,
                                    pairs=pairs)
+    Q2, K2 = torch.full_like(Q1, 7.0), torch.full_like(Q1, 7.0)
+    assert ops.linear_qk_norm_rope(X, W[:2 * d], bias[:2 * d], wq, wk, cos, sin, Q2, K2, B, H, S, rows, s0, K, q_scale=q_scale,
+                                   pairs=pairs)
+    assert torch.equal(Q2, Q1) and torch.equal(K2, K1)
+    del Q2, K2
     qkv = torch.zeros(tokens, 3 * d, dtype=torch.bfloat16, device="cuda")
     sk_default = ops.GEMM_STREAM_K
     ops.GEMM_STREAM_K = False
