@@ -247,8 +247,12 @@ int mgx_qk_norm_rope_bwd_qs(const uint16_t* qkv, long ld, const float* wq, const
                             int rows_per_batch, int s0, float q_scale, void* stream);
 
 /* O = softmax(scale * Q K^T) V, non-causal, head_dim 128 (F.scaled_dot_product_attention under autocast):
- * Q,K [B,H,S,128], Vt [B,H,128,Sp] (Sp = S rounded up to 64, padding finite), O [B,S,ldo] at column h*128,
- * lse [B,H,S] (optional, natural log) for the backward pass. */
+ * Q,K [B,H,S,128], Vt [B,H,128,Sp], O [B,S,ldo] at column h*128 (columns outside the head blocks and the gap between
+ * batches when o_bstride > S * ldo are not written), lse [B,H,S] (optional, natural log) for the backward pass.
+ * Sp: any multiple of 64 that is >= S.  The padding columns s >= S of Vt (and of Qt, Kt, below) are read and multiplied by
+ * probabilities that are exactly zero, so they may hold ANY FINITE values (not NaN / inf: 0 * inf); they are never written.
+ * Sp > S with S % 256 == 0 (more padding than S rounded up to 64 needs) is accepted but costs the generated 64-wide kernels:
+ * those take Sp == S only, the 8-wave kernels run instead (mgx_attn_fwd_path / mgx_attn_bwd_path tell). */
 int mgx_attn_fwd(const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, uint16_t* O, float* lse, int B, int H, int S,
                  int Sp, long ldo, long o_bstride, float scale, void* stream);
 
@@ -257,6 +261,13 @@ int mgx_attn_fwd(const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, uint1
  * starts at -m -- and the per-score multiply-add of the softmax is gone (csrc/gen/attn_fwd64.py, ACC). */
 int mgx_attn_fwd_log2(const uint16_t* Q2, const uint16_t* K, const uint16_t* Vt, uint16_t* O, float* lse, int B, int H,
                       int S, int Sp, long ldo, long o_bstride, void* stream);
+
+/* Which kernels mgx_attn_fwd / mgx_attn_fwd_log2 and mgx_attn_bwd launch for a problem: 0 = the 8-wave kernels, 1 = the
+ * generated 64-wide ones (S % 256 == 0, Sp == S, offsets within their 32-bit / 24-bit fields; the forward also needs the
+ * persistent walk's stride / (S / 256) < H, csrc/attention.hip), negative = the sizes are refused.  The launchers call the
+ * same predicate; MGX_ATTN_W64=0 (read per call) forces 0.  Launches nothing. */
+int mgx_attn_fwd_path(int B, int H, int S, int Sp, long ldo, long o_bstride);
+int mgx_attn_bwd_path(int B, int H, int S, int Sp, long ldo, long o_bstride);
 
 /* fp8 (OCP e4m3) variant of mgx_attn_fwd: the "fp8 MFMA attention path" of BASELINE.json configs[4].  The reference
  * has no fp8 attention; the entry points serve the same SDPA call sites (fastvideo/utils/sampling_utils.py:68-82,
@@ -272,8 +283,10 @@ int mgx_attn_fwd_fp8(const uint8_t* Q8, const uint8_t* K8, const uint8_t* V8t, c
                      float* lse, int B, int H, int S, int Sp, long ldo, long o_bstride, float scale, void* stream);
 
 /* Backward of mgx_attn_fwd (P recomputed from lse): dQ, dK, dV [B,H,S,128].  Inputs Q,K,V row-major, Qt,Kt
- * [B,H,128,Sp] (mgx_qk_norm_rope_fwd extras), O and dO [B,S,ldo] at column h*128.  delta [B,H,S] fp32 and dOt
- * [B,H,128,Sp] bf16 are caller-provided scratch filled by the internal prep kernel. */
+ * [B,H,128,Sp] (mgx_qk_norm_rope_fwd extras; padding columns s >= S finite, see mgx_attn_fwd), O and dO [B,S,ldo] at
+ * column h*128.  delta [B,H,S] fp32 and dOt [B,H,128,Sp] bf16 are caller-provided scratch that the internal prep kernel
+ * fills completely: delta[b,h,s] = sum_d dO * O in fp32 from the bf16 O passed in (the forward's rounded output, not its
+ * fp32 accumulator), dOt = the head's dO columns transposed, zero in the padding columns s >= S (nothing beyond Sp). */
 int mgx_attn_bwd(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* Qt, const uint16_t* Kt,
                  const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt, uint16_t* dQ,
                  uint16_t* dK, uint16_t* dV, int B, int H, int S, int Sp, long ldo, long o_bstride, float scale,

@@ -393,6 +393,23 @@ __global__ void __launch_bounds__(256, 1) attn_fwd64_kernel(AttnArgs g) {
 
 }  // namespace
 
+// Which forward kernel a problem gets: 1 = attn_fwd64_kernel (grid64 workgroups), 0 = attn_fwd_kernel.  The ONE predicate of
+// attn_fwd_any and of the mgx_attn_fwd_path query.
+static bool attn_fwd_wide(int B, int H, int S, int Sp, long ldo, long o_bstride, int* grid64_out) {
+  const char* w64e = getenv("MGX_ATTN_W64");   // read per call: tests switch kernels inside one process
+  const int w64 = w64e ? atoi(w64e) : 1;
+  // The persistent walk advances (q-tile, head, batch) by a fixed stride and carries ONCE per step (gen/attn_fwd64.py,
+  // block_advance_stores: head -= H, batch += 1), so a step must move the head index by less than H: stride / nq < H.
+  // (FLUX: H = 24, nq >= 3, stride 32.)  Shapes outside that -- S = 256 with many batches, few heads -- take attn_fwd_kernel.
+  const long nblk64 = (long)(S / 256) * H * B;
+  const int grid64 = nblk64 >= 256 ? 256 : (int)nblk64;
+  const int stride64 = (grid64 & 7) == 0 ? grid64 >> 3 : grid64;
+  const bool walk_ok = S >= 256 && stride64 / (S / 256) < H;
+  if (grid64_out) *grid64_out = grid64;
+  return w64 && walk_ok && S % 256 == 0 && Sp == S && (long)S * ldo * 2 < (1L << 31) && o_bstride * 2 < (1L << 31) &&
+         (long)S * 256 < (1L << 31);
+}
+
 static int attn_fwd_any(const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, uint16_t* O, float* lse, int B, int H, int S,
                         int Sp, long ldo, long o_bstride, float scale_log2e, bool log2_scores, void* stream) {
   MGX_REQUIRE(Q && K && Vt && O, "null operand");
@@ -408,17 +425,8 @@ static int attn_fwd_any(const uint16_t* Q, const uint16_t* K, const uint16_t* Vt
   const int lds = 2 * (K_TILE_BYTES + V_TILE_BYTES);
   hipStream_t st = (hipStream_t)stream;
   static const int ovl = getenv("MGX_ATTN_OVL") ? atoi(getenv("MGX_ATTN_OVL")) : 1;
-  const char* w64e = getenv("MGX_ATTN_W64");   // read per call: tests switch kernels inside one process
-  const int w64 = w64e ? atoi(w64e) : 1;
-  // The persistent walk advances (q-tile, head, batch) by a fixed stride and carries ONCE per step (gen/attn_fwd64.py,
-  // block_advance_stores: head -= H, batch += 1), so a step must move the head index by less than H: stride / nq < H.
-  // (FLUX: H = 24, nq >= 3, stride 32.)  Shapes outside that -- S = 256 with many batches, few heads -- take attn_fwd_kernel.
-  const long nblk64 = (long)(S / 256) * H * B;
-  const int grid64 = nblk64 >= 256 ? 256 : (int)nblk64;
-  const int stride64 = (grid64 & 7) == 0 ? grid64 >> 3 : grid64;
-  const bool walk_ok = S >= 256 && stride64 / (S / 256) < H;
-  if (w64 && walk_ok && S % 256 == 0 && Sp == S && (long)S * ldo * 2 < (1L << 31) && o_bstride * 2 < (1L << 31) &&
-      (long)S * 256 < (1L << 31)) {
+  int grid64 = 0;
+  if (attn_fwd_wide(B, H, S, Sp, ldo, o_bstride, &grid64)) {
     static bool attr = false;
     if (!attr) {
       (void)hipFuncSetAttribute((const void*)attn_fwd64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
@@ -447,4 +455,10 @@ extern "C" int mgx_attn_fwd(const uint16_t* Q, const uint16_t* K, const uint16_t
 extern "C" int mgx_attn_fwd_log2(const uint16_t* Q2, const uint16_t* K, const uint16_t* Vt, uint16_t* O, float* lse, int B,
                                  int H, int S, int Sp, long ldo, long o_bstride, void* stream) {
   return attn_fwd_any(Q2, K, Vt, O, lse, B, H, S, Sp, ldo, o_bstride, 1.0f, true, stream);
+}
+
+extern "C" int mgx_attn_fwd_path(int B, int H, int S, int Sp, long ldo, long o_bstride) {
+  MGX_REQUIRE(B > 0 && H > 0 && S > 0, "empty attention");
+  MGX_REQUIRE(Sp >= S && Sp % 64 == 0, "Sp must be S rounded up to a multiple of 64");
+  return attn_fwd_wide(B, H, S, Sp, ldo, o_bstride, nullptr) ? 1 : 0;
 }

@@ -564,6 +564,15 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_dkv64_kernel(BwdArgs g) {
 
 }  // namespace
 
+// Which backward kernels a problem gets: 1 = the generated 64-wide pair, 0 = the 8-wave pair.  The ONE predicate of mgx_attn_bwd
+// and of the mgx_attn_bwd_path query.
+static bool attn_bwd_wide(int B, int H, int S, int Sp, long ldo, long o_bstride) {
+  const char* w64e = getenv("MGX_ATTN_W64");        // read per call: tests switch kernels inside one process
+  const int w64 = w64e ? atoi(w64e) : 1;
+  // the generated 64-wide kernels: S % 256 == 0, 32-bit offsets inside a 256-row block of dO, 24-bit row * ldo products
+  return w64 && S % 256 == 0 && Sp == S && ldo * 2 * 256 < (1L << 31) && ldo * 2 < (1L << 24) && Sp * 2 < (1L << 24);
+}
+
 extern "C" int mgx_attn_bwd(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* Qt, const uint16_t* Kt,
                             const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt,
                             uint16_t* dQ, uint16_t* dK, uint16_t* dV, int B, int H, int S, int Sp, long ldo, long o_bstride,
@@ -584,11 +593,7 @@ extern "C" int mgx_attn_bwd(const uint16_t* Q, const uint16_t* K, const uint16_t
     attr = true;
   }
   const int nb = cdiv(S, 256) * H * B;
-  const char* w64e = getenv("MGX_ATTN_W64");        // read per call: tests switch kernels inside one process
-  const int w64 = w64e ? atoi(w64e) : 1;
-  // the generated 64-wide kernels: S % 256 == 0, 32-bit offsets inside a 256-row block of dO, 24-bit row * ldo products
-  const bool wide = w64 && S % 256 == 0 && Sp == S && ldo * 2 * 256 < (1L << 31) && ldo * 2 < (1L << 24) && Sp * 2 < (1L << 24);
-  if (wide) {
+  if (attn_bwd_wide(B, H, S, Sp, ldo, o_bstride)) {
     static bool attr64 = false;
     if (!attr64) {
       (void)hipFuncSetAttribute((const void*)attn_bwd_dq64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
@@ -603,4 +608,9 @@ extern "C" int mgx_attn_bwd(const uint16_t* Q, const uint16_t* K, const uint16_t
   }
   MGX_CHECK_LAUNCH();
   return MGX_OK;
+}
+
+extern "C" int mgx_attn_bwd_path(int B, int H, int S, int Sp, long ldo, long o_bstride) {
+  MGX_REQUIRE(B > 0 && H > 0 && S > 0 && Sp >= S && Sp % 64 == 0, "bad sizes");
+  return attn_bwd_wide(B, H, S, Sp, ldo, o_bstride) ? 1 : 0;
 }

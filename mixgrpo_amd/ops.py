@@ -228,6 +228,20 @@ def attn_fwd_log2(Q2, K, Vt, O_ptr_tensor, lse, B, H, S, Sp, ldo, o_bstride):
                                   stream()))
 
 
+def attn_fwd_path(B, H, S, Sp, ldo, o_bstride):
+    """The kernel attn_fwd / attn_fwd_log2 launch for this problem: 0 = 8-wave, 1 = the generated 64-query one."""
+    r = lib().mgx_attn_fwd_path(B, H, S, Sp, ldo, o_bstride)
+    check(min(r, 0))
+    return r
+
+
+def attn_bwd_path(B, H, S, Sp, ldo, o_bstride):
+    """The kernels attn_bwd launches for this problem: 0 = 8-wave dkv / dq, 1 = the generated 64-wide pair."""
+    r = lib().mgx_attn_bwd_path(B, H, S, Sp, ldo, o_bstride)
+    check(min(r, 0))
+    return r
+
+
 def attn_fp8_quantize(Q, K, Vt, Q8, K8, V8t, amax, B, H, S, Sp):
     """Per-(batch, head) e4m3 quantisation of the attention operands (csrc/attention_fp8.hip)."""
     check(lib().mgx_attn_fp8_quantize(ptr(Q), ptr(K), ptr(Vt), ptr(Q8), ptr(K8), ptr(V8t), ptr(amax), B, H, S, Sp,

@@ -107,12 +107,18 @@ def _reference(q2, k, v):
     return s, (torch.softmax(s, -1) @ v.float()).transpose(1, 2).reshape(B, S, H * 128)
 
 
-@pytest.mark.parametrize("B,H,S,ldo_mult", [(1, 1, 256, 1), (2, 3, 768, 5), (1, 24, 1536, 1), (2, 3, 1100, 1)])
+# which kernel mgx_attn_fwd_log2 takes with MGX_ATTN_W64 unset or 1 (tests/test_hip_mmdit.py::FWD64_PATH explains the two zeros)
+FWD64_PATH = {(1, 1, 256): 0, (2, 3, 768): 0, (1, 24, 1536): 1, (2, 3, 1100): 0, (2, 4, 512): 1, (3, 8, 512): 1}
+
+
+@pytest.mark.parametrize("B,H,S,ldo_mult", [(1, 1, 256, 1), (2, 3, 768, 5), (1, 24, 1536, 1), (2, 3, 1100, 1), (2, 4, 512, 1),
+                                            (3, 8, 512, 5)])
 def test_attention_log2_vs_torch_and_vs_the_8_wave_kernel(B, H, S, ldo_mult, monkeypatch):
     """mgx_attn_fwd_log2 on Q2 = bf16(q c) against fp32 softmax(ln 2 * Q2 K^T) V of the same operands (<= 6e-3 relative L2,
-    lse 1e-4), on the 64-query kernel (S % 256 == 0) and on the 8-wave kernel (MGX_ATTN_W64=0 / S = 1100 with padding); the two
-    agree within bf16 rounding of O; columns beyond the head block stay untouched; and against mgx_attn_fwd(Q2, scale = ln 2),
-    the same mathematics through the multiply-add softmax."""
+    lse 1e-4), on the 64-query kernel (the shapes with FWD64_PATH 1) and on the 8-wave kernel (MGX_ATTN_W64=0, S = 1100 with
+    padding, and (1, 1, 256) / (2, 3, 768), which the walk cannot take: their two legs run the same kernel); the two agree
+    within bf16 rounding of O; columns beyond the head block stay untouched; and against mgx_attn_fwd(Q2, scale = ln 2), the
+    same mathematics through the multiply-add softmax.  Each leg asserts the kernel it ran."""
     from mixgrpo_amd import ops
     g = torch.Generator(device="cuda").manual_seed(S + H)
     q, k, v = (torch.randn(B, H, S, 128, device="cuda", generator=g).bfloat16() for _ in range(3))
@@ -124,11 +130,13 @@ def test_attention_log2_vs_torch_and_vs_the_8_wave_kernel(B, H, S, ldo_mult, mon
     outs = []
     for w64 in ("1", "0"):
         monkeypatch.setenv("MGX_ATTN_W64", w64)
+        assert ops.attn_fwd_path(B, H, S, Sp, ldo, S * ldo) == (FWD64_PATH[(B, H, S)] if w64 == "1" else 0)
         O = torch.zeros(B, S, ldo, device="cuda", dtype=torch.bfloat16)
         lse = torch.empty(B, H, S, device="cuda")
         ops.attn_fwd_log2(q2, k, vt, O, lse, B, H, S, Sp, ldo, S * ldo)
         outs.append((O, lse))
     monkeypatch.setenv("MGX_ATTN_W64", "1")
+    assert ops.attn_fwd_path(B, H, S, Sp, ldo, S * ldo) == FWD64_PATH[(B, H, S)]
     O = torch.zeros(B, S, ldo, device="cuda", dtype=torch.bfloat16)
     lse = torch.empty(B, H, S, device="cuda")
     ops.attn_fwd(q2, k, vt, O, lse, B, H, S, Sp, ldo, S * ldo, LN2)
@@ -156,6 +164,7 @@ def test_attention_log2_rescale_path():
     q2 = (q.float() * C).bfloat16()
     O = torch.empty(B, S, H * 128, device="cuda", dtype=torch.bfloat16)
     lse = torch.empty(B, H, S, device="cuda")
+    assert ops.attn_fwd_path(B, H, S, S, H * 128, S * H * 128) == 1           # attn_fwd64q: the fix-up is its code
     ops.attn_fwd_log2(q2, k, v.transpose(-1, -2).contiguous(), O, lse, B, H, S, S, H * 128, S * H * 128)
     s, ref = _reference(q2, k, v)
     assert torch.isfinite(O.float()).all()

@@ -166,11 +166,20 @@ def test_attention_deferred_rescale_paths(growth):
     assert torch.allclose(lse, torch.logsumexp(s, -1), rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("B,H,S,ldo_mult", [(1, 1, 256, 1), (2, 3, 768, 5), (1, 24, 1536, 1)])
+# the kernel mgx_attn_fwd* takes with MGX_ATTN_W64 unset or 1 (ops.attn_fwd_path): S % 256 == 0 is not enough, the persistent
+# walk needs stride / nq < H (csrc/attention.hip).  (1, 1, 256): one block, stride 1, 1 / 1 < 1 fails; (2, 3, 768): 18 blocks, not
+# a multiple of 8, stride 18, 18 / 3 < 3 fails -- both are 8-wave cases on either setting of the switch.
+FWD64_PATH = {(1, 1, 256): 0, (2, 3, 768): 0, (1, 24, 1536): 1, (2, 4, 512): 1, (3, 8, 512): 1}
+
+
+@pytest.mark.parametrize("B,H,S,ldo_mult", [(1, 1, 256, 1), (2, 3, 768, 5), (1, 24, 1536, 1), (2, 4, 512, 1), (3, 8, 512, 5)])
 def test_attention_fwd64_vs_torch_and_vs_the_8_wave_kernel(B, H, S, ldo_mult, monkeypatch):
-    """The 64-query-wave forward (S % 256 == 0: generated instruction stream, csrc/gen/attn_fwd64.py) against an fp32 torch
-    softmax(Q K^T / sqrt(d)) V, and against the 8-wave kernel on the same operands (MGX_ATTN_W64=0): same tolerance to the
-    reference, agreement between the two within bf16 rounding of O, columns beyond the head block untouched."""
+    """The 64-query-wave forward (generated instruction stream, csrc/gen/attn_fwd64.py; shapes with FWD64_PATH 1: B > 1, a walk
+    that carries into the next batch) against an fp32 torch softmax(Q K^T / sqrt(d)) V, and against the 8-wave kernel on the same
+    operands (MGX_ATTN_W64=0): same tolerance to the reference, agreement between the two within bf16 rounding of O, columns
+    beyond the head block untouched.  (1, 1, 256) and (2, 3, 768) have S % 256 == 0 but take the 8-wave kernel on both legs
+    (FWD64_PATH 0): for them the comparison of the two legs is a comparison of that kernel with itself.  Each leg asserts the
+    kernel it ran; tests/test_hip_attention_kernels.py holds the per-row float64 checks."""
     from mixgrpo_amd import ops
     g = torch.Generator(device="cuda").manual_seed(S + H)
     q, k, v = (torch.randn(B, H, S, 128, device="cuda", generator=g).bfloat16() for _ in range(3))
@@ -179,6 +188,7 @@ def test_attention_fwd64_vs_torch_and_vs_the_8_wave_kernel(B, H, S, ldo_mult, mo
     outs = []
     for w64 in ("1", "0"):
         monkeypatch.setenv("MGX_ATTN_W64", w64)
+        assert ops.attn_fwd_path(B, H, S, S, ldo, S * ldo) == (FWD64_PATH[(B, H, S)] if w64 == "1" else 0)
         O = torch.zeros(B, S, ldo, device="cuda", dtype=torch.bfloat16)
         lse = torch.empty(B, H, S, device="cuda")
         ops.attn_fwd(q, k, vt, O, lse, B, H, S, S, ldo, S * ldo, 1 / math.sqrt(128))
@@ -207,6 +217,7 @@ def test_attention_fwd64_rescale_path():
     k[:, :, 333] = (7 * q[:, :, 700].float()).bfloat16()       # third query block
     O = torch.empty(B, S, H * 128, device="cuda", dtype=torch.bfloat16)
     lse = torch.empty(B, H, S, device="cuda")
+    assert ops.attn_fwd_path(B, H, S, S, H * 128, S * H * 128) == 1           # the 64-query kernel: the fix-up is its code
     ops.attn_fwd(q, k, v.transpose(-1, -2).contiguous(), O, lse, B, H, S, S, H * 128, S * H * 128, 1 / math.sqrt(128))
     s = (q.float() @ k.float().transpose(-1, -2)) / math.sqrt(128)
     ref = (torch.softmax(s, -1) @ v.float()).transpose(1, 2).reshape(B, S, H * 128)
@@ -237,6 +248,7 @@ def test_attention_bwd64_vs_autograd_and_vs_the_8_wave_kernels(B, H, S, ldo_mult
     outs = []
     for w64 in ("1", "0"):
         monkeypatch.setenv("MGX_ATTN_W64", w64)
+        assert ops.attn_bwd_path(B, H, S, S, ldo, S * ldo) == int(w64)        # the backward has no walk: every S % 256 == 0 shape
         O = torch.zeros(B, S, ldo, device="cuda", dtype=torch.bfloat16)
         lse = torch.empty(B, H, S, device="cuda")
         ops.attn_fwd(q, k, vt, O, lse, B, H, S, S, ldo, S * ldo, 1 / math.sqrt(128))
