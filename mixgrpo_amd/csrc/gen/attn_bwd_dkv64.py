@@ -24,14 +24,15 @@ LDS (146 KiB): Q | dO row-major tiles, 3 slots (read addresses rotate in a regis
 iterations ahead (Q | dO, lse | delta) so that the first fragments of an iteration are read before the barrier in front of it.
 The `s_waitcnt lgkmcnt` in front of each MFMA is derived from the in-order LDS queue by the generator.
 Checked on the CPU by tests/test_attn_bwd64_emulated.py (interpreter + hazard pass) before it runs on a GPU.
+
+What every stream needs alike (line buffer, counted loop, lane decode and pi(r), the LDS-DMA idiom, the store block, the .inc
+text) comes from csrc/gen/emit.py; this kernel's tile images are its own (32-query tiles, 64-byte transposed rows).
 """
 import os
-import sys
+from collections import namedtuple
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from attn_fwd64 import Asm, a, ar, s, sr, v, vr  # noqa: E402
-
-MFMA = "v_mfma_f32_32x32x16_bf16"
+import emit
+from emit import MFMA, Asm, a, ar, s, sr, v, vr
 
 # ------------------------------------------------------------------------------------------------ register map
 DV_A, DV_B, DK_A, DK_B = 0, 64, 128, 192
@@ -60,11 +61,7 @@ LDS_BYTES = VP_BASE + 4 * 16384
 LEAD = 5                         # gaps between a fragment's ds_read and its first MFMA
 
 
-class Chain:
-    def __init__(self, name, DV, DK, KF, S, DP, P, DS):
-        self.name, self.DV, self.DK, self.KF, self.S, self.DP, self.P, self.DS = name, DV, DK, KF, S, DP, P, DS
-
-
+Chain = namedtuple("Chain", "name DV DK KF S DP P DS")
 CHAINS = (Chain("a", DV_A, DK_A, KF_A, S_A, DP_A, P_A, DS_A), Chain("b", DV_B, DK_B, KF_B, S_B, DP_B, P_B, DS_B))
 
 
@@ -244,9 +241,7 @@ def c_dma(A):
     A.e(f"s_min_u32 {s(sTMP)}, {s(sCOFF)}, {s(sCMAX)}")
     A.e(f"v_add_co_u32 {v(X)}, vcc, {s(sTMP)}, {v(CSRC)}")
     A.e(f"v_addc_co_u32 {v(X + 1)}, vcc, 0, {v(CSRC + 1)}, vcc")
-    A.e(f"s_mov_b32 m0, {s(sCDST)}")
-    A.e("s_nop 0")
-    A.e(f"global_load_lds_dword {vr(X, 2)}, off")
+    emit.lds_dma(A, (f"s_mov_b32 m0, {s(sCDST)}", f"global_load_lds_dword {vr(X, 2)}, off"))
     A.label(skip)
     A.e(f"s_add_u32 {s(sCOFF)}, {s(sCOFF)}, 128")
 
@@ -288,9 +283,7 @@ def emit_iteration(A, par, first=False, last=False):
             if m0w.startswith(f"s_add_i32 m0, {s(sQDST)}"):    # Q | dO pieces: m0 = rotating slot + w * 2048 + piece
                 A.e(f"s_add_u32 {s(sTMP)}, {s(sQDST)}, {s(sWOFF2)}")
                 m0w = m0w.replace(s(sQDST), s(sTMP))
-            A.e(m0w)
-            A.e(fill.pop(0) if fill else "s_nop 0")
-            A.e(ld)
+            emit.lds_dma(A, (m0w, ld), fill)
         for x in fill:
             A.e(x)
         if g == 30 and not last:
@@ -318,25 +311,10 @@ def prologue(A):
     for dst, nm in ((sSP2, "sp2"), (sLDO2, "ldo2"), (sCS, "cs"), (sSCALE, "scale"), (sNIS, "nis"), (sNLOOP, "nloop"),
                     (sQMAX, "qmax"), (sLDO32, "ldo32"), (sCMAX, "cmax")):
         A.e(f"s_mov_b32 {s(dst)}, %[{nm}]")
-    lane, w, r, h = v(RING), v(RING + 1), v(RING + 2), v(RING + 3)       # the ring is free in the prologue
-    t0, t1, t2, t3 = v(RING + 4), v(RING + 5), v(RING + 6), v(RING + 7)
-    A.e(f"v_and_b32 {lane}, 63, %[tid]")
-    A.e(f"v_lshrrev_b32 {w}, 6, %[tid]")
-    A.e(f"v_and_b32 {r}, 31, {lane}")
-    A.e(f"v_lshrrev_b32 {h}, 5, {lane}")
-    A.e(f"v_readfirstlane_b32 {s(sW)}, {w}")
-    A.e(f"s_lshl_b32 {s(sWOFF2)}, {s(sW)}, 11")
+    L = emit.lane_decode(A, RING, s_wave=sW, s_woff=sWOFF2, woff_shift=11)     # the ring is free in the prologue
+    lane, w, r, h, t0, t1, t2, t3 = L.lane, L.w, L.r, L.h, L.t0, L.t1, L.t2, v(RING + 7)
     A.c("Q | dO fragment reads: MFMA row r reads tile row pi(r) (bits 2, 3 exchanged), chunk (2 ks + h) ^ (row & 15)")
-    pi = v(RING + 8)
-    A.e(f"v_and_b32 {t0}, 0x13, {r}")
-    A.e(f"v_and_b32 {t1}, 4, {r}")
-    A.e(f"v_lshlrev_b32 {t1}, 1, {t1}")
-    A.e(f"v_and_b32 {t2}, 8, {r}")
-    A.e(f"v_lshrrev_b32 {t2}, 1, {t2}")
-    A.e(f"v_or3_b32 {pi}, {t0}, {t1}, {t2}")
-    A.e(f"v_and_b32 {t0}, 15, {pi}")
-    A.e(f"v_xor_b32 {t0}, {h}, {t0}")
-    A.e(f"v_lshlrev_b32 {t1}, 8, {pi}")
+    emit.row_permutation(A, L, pi=v(RING + 8), xk=t0, pi8=t1)
     A.e(f"v_lshl_add_u32 {v(QB0)}, {t0}, 4, {t1}")
     A.c("V fragments, wave-private: [chain][ks][lane] 16-byte pieces")
     A.e(f"v_lshlrev_b32 {t0}, 4, {lane}")
@@ -405,9 +383,8 @@ def prologue(A):
     for ci in range(2):
         for ks in range(8):
             # (an LDS-DMA's instruction offset is added to the LDS address too: m0 takes it back out)
-            A.e(f"s_add_i32 m0, {s(sTMP)}, {ci * 8192 + ks * 1024 - 32 * ks}")
-            A.e("s_nop 0")
-            A.e(f"global_load_lds_dwordx4 {v(RING + 10 + ci)}, {sr(sDOP, 2)} offset:{32 * ks}")
+            emit.lds_dma(A, (f"s_add_i32 m0, {s(sTMP)}, {ci * 8192 + ks * 1024 - 32 * ks}",
+                             f"global_load_lds_dwordx4 {v(RING + 10 + ci)}, {sr(sDOP, 2)} offset:{32 * ks}"))
     A.c("first tiles: Q | dO of blocks 0, 1 -> slots 0, 1; lse | delta of blocks 0, 1 -> slots 0, 1")
     A.e(f"s_mov_b32 {s(sQROW)}, 0")
     A.e(f"s_mov_b32 {s(sTT)}, 0")
@@ -421,9 +398,8 @@ def prologue(A):
         A.e(f"s_add_u32 {s(sTMP)}, {s(sQDST)}, {s(sWOFF2)}")
         for off, ptr, src in ((0, sQP, QSRC), (8192, sDOP, DOSRC)):
             for p in range(2):
-                A.e(f"s_add_i32 m0, {s(sTMP)}, {off + p * 1024}")
-                A.e("s_nop 0")
-                A.e(f"global_load_lds_dwordx4 {v(src + p)}, {sr(ptr, 2)}")
+                emit.lds_dma(A, (f"s_add_i32 m0, {s(sTMP)}, {off + p * 1024}",
+                                 f"global_load_lds_dwordx4 {v(src + p)}, {sr(ptr, 2)}"))
         A.e(f"s_add_u32 {s(sCDST)}, {s(sCDST)}, 256")
         c_dma(A)
     A.e(f"s_mov_b32 {s(sQRD)}, 0")
@@ -461,12 +437,8 @@ def epilogue(A):
     A.e("s_nop 7")
     A.e("s_nop 7")
     A.c("================ epilogue: dV, dK * scale -> bf16, 16-byte stores (lane halves exchanged pairwise)")
-    lane, w, r, h, t0 = v(RING), v(RING + 1), v(RING + 2), v(RING + 3), v(RING + 4)
-    off_a, off_b = v(RING + 5), v(RING + 6)
-    A.e(f"v_and_b32 {lane}, 63, %[tid]")
-    A.e(f"v_lshrrev_b32 {w}, 6, %[tid]")
-    A.e(f"v_and_b32 {r}, 31, {lane}")
-    A.e(f"v_lshrrev_b32 {h}, 5, {lane}")
+    L = emit.lane_decode(A, RING)
+    w, r, h, t0, off_a, off_b = L.w, L.r, L.h, L.t0, v(RING + 5), v(RING + 6)
     A.e(f"v_lshl_add_u32 {t0}, {w}, 6, {r}")
     A.e(f"v_lshlrev_b32 {t0}, 8, {t0}")
     A.e(f"v_lshl_add_u32 {off_a}, {h}, 4, {t0}")
@@ -475,26 +447,10 @@ def epilogue(A):
     A.e(f"s_mov_b32 {s(sDK + 1)}, %[dk_hi]")
     A.e(f"s_mov_b32 {s(sDV)}, %[dv_lo]")
     A.e(f"s_mov_b32 {s(sDV + 1)}, %[dv_hi]")
-    E0 = RING + 8                                        # 4 staging quads RING+8 .. RING+23, 8 read registers RING+24 .. +31
-    cnt = 0
-    for acc, ptr, scaled in ((DV_A, sDV, False), (DV_B, sDV, False), (DK_A, sDK, True), (DK_B, sDK, True)):
-        off = off_a if acc in (DV_A, DK_A) else off_b
-        for dt in range(4):
-            for g in (0, 2):
-                E = E0 + 4 * (cnt & 3)
-                cnt += 1
-                rd = [v(RING + 24 + j) for j in range(8)]
-                for j in range(8):
-                    A.e(f"v_accvgpr_read_b32 {rd[j]}, {a(acc + 16 * dt + 4 * g + j)}")
-                if scaled:
-                    for j in range(8):
-                        A.e(f"v_mul_f32 {rd[j]}, {rd[j]}, {s(sSCALE)}")
-                for j in range(4):
-                    A.e(f"v_cvt_pk_bf16_f32 {v(E + j)}, {rd[2 * j]}, {rd[2 * j + 1]}")
-                A.e("s_nop 1")
-                A.e(f"v_permlane32_swap_b32 {v(E)}, {v(E + 2)}")
-                A.e(f"v_permlane32_swap_b32 {v(E + 1)}, {v(E + 3)}")
-                A.e(f"global_store_dwordx4 {off}, {vr(E, 4)}, {sr(ptr, 2)} offset:{64 * dt + 16 * g}")
+    # 4 staging quads RING+8 .. RING+23, 8 read registers RING+24 .. +31
+    for acc, ptr, mul, off in ((DV_A, sDV, None, off_a), (DV_B, sDV, None, off_b),
+                               (DK_A, sDK, s(sSCALE), off_a), (DK_B, sDK, s(sSCALE), off_b)):
+        emit.store_acc_bf16(A, acc, mul, RING + 8, RING + 24, off, ptr)
 
 
 def generate():
@@ -503,26 +459,10 @@ def generate():
     for fid in sorted((f for f in PLAN if PLAN[f][1] - LEAD < 0), key=lambda f: PLAN[f][1]):
         A.e(read_instr(fid, 0))
     emit_iteration(A, 0, first=True)
-    A.e(f"s_mov_b32 {s(sLOOP)}, {s(sNLOOP)}")
-    loop, done = A.new_label("loop"), A.new_label("loopdone")
-    A.e(f"s_cmp_eq_u32 {s(sLOOP)}, 0")
-    A.e(f"s_cbranch_scc1 {done}")
-    A.label(loop)
-    emit_iteration(A, 1)
-    emit_iteration(A, 0)
-    A.e(f"s_sub_u32 {s(sLOOP)}, {s(sLOOP)}, 1")
-    A.e(f"s_cmp_lg_u32 {s(sLOOP)}, 0")
-    A.e(f"s_cbranch_scc1 {loop}")
-    A.label(done)
+    emit.counted_loop(A, sLOOP, sNLOOP, lambda: emit_iteration(A, 1), lambda: emit_iteration(A, 0))
     emit_iteration(A, 1, last=True)
     epilogue(A)
     return A.text()
-
-
-def clobbers():
-    regs = [f"v{i}" for i in range(4, V_LAST + 1)] + [f"a{i}" for i in range(256)] + \
-           [f"s{i}" for i in range(S_FIRST, S_LAST + 1)] + ["vcc", "scc", "memory"]
-    return ", ".join(f'"{x}"' for x in regs)
 
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -530,27 +470,12 @@ OUT_BODY = os.path.join(HERE, "..", "attn_bwd_dkv64_body.inc")
 
 
 def render():
-    body = generate()
-    lines = ["// GENERATED by mixgrpo_amd/csrc/gen/attn_bwd_dkv64.py -- do not edit; see that file for the design.",
-             "#define ATTN_BWD_DKV64_CLOBBERS " + clobbers(),
-             "#define ATTN_BWD_DKV64_BODY \\"]
-    for ln in body.rstrip("\n").split("\n"):
-        lines.append('  "' + ln.replace("\\", "\\\\").replace('"', '\\"') + '\\n" \\')
-    lines.append('  ""')
-    return "\n".join(lines) + "\n"
+    return emit.render("ATTN_BWD_DKV64", __file__, generate(), emit.clobbers(V_LAST, S_FIRST, S_LAST))
 
 
 def write(path=OUT_BODY):
-    txt = render()
-    old = open(path).read() if os.path.exists(path) else None
-    if old != txt:
-        with open(path, "w") as f:
-            f.write(txt)
-    return path
+    return emit.write_if_changed(path, render())
 
 
 if __name__ == "__main__":
-    if "--print" in sys.argv:
-        sys.stdout.write(generate())
-    else:
-        print(write())
+    emit.main(generate, write)

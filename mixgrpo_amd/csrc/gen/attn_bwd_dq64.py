@@ -4,7 +4,8 @@
 dQ of the joint attention backward (autograd of F.scaled_dot_product_attention at the reference's call site
 fastvideo/train_grpo_flux.py:134-144), for S % 256 == 0; the 8-wave kernel of round 1 / 2 stays for other shapes.
 
-Same construction as the forward (csrc/gen/attn_fwd64.py: read that first): one wave per SIMD, a wave owns 64 queries =
+Same construction as the forward (the docstring of csrc/gen/attn_fwd64.py: read that first; what the two files emit alike --
+the K and V^T tile images, `segment`, the store block -- is in csrc/gen/emit.py): one wave per SIMD, a wave owns 64 queries =
 chains a and b of 32, and every K / V / K^T fragment read from LDS feeds both chains.  Per 32-key block j and chain c:
     QK(c, j):  S^T = K Q_c^T (8 MFMAs)  and  dP^T = V dO_c^T (8 MFMAs)         [key on the row, query on the lane]
     SM(c, j):  p = exp2(s c - lse_q log2 e),  ds = p (dp - delta_q)            [4.5 VALU per element, no maximum: lse is known]
@@ -22,12 +23,10 @@ second half does not exist in the last interval: waves 2, 3, whose DMA pieces it
 dQ is scaled by `scale` in the epilogue (dS carries no scale).  Checked on the CPU by tests/test_attn_bwd64_emulated.py.
 """
 import os
-import sys
+from collections import namedtuple
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from attn_fwd64 import Asm, a, ar, s, sr, v, vr  # noqa: E402
-
-MFMA = "v_mfma_f32_32x32x16_bf16"
+import emit
+from emit import MFMA, Asm, a, ar, s, sr, spread, v, vr
 
 # ------------------------------------------------------------------------------------------------ register map
 DQ_A, DQ_B = 0, 64
@@ -59,10 +58,7 @@ K_BASE, V_BASE, KT_BASE = 0, 32768, 65536
 SLOT = 16384
 
 
-class Chain:
-    def __init__(self, name, DQ, QF, DOF, S, DP, DS, LSE, DL):
-        self.name, self.DQ, self.QF, self.DOF, self.S, self.DP, self.DS, self.LSE, self.DL = name, DQ, QF, DOF, S, DP, DS, LSE, DL
-
+Chain = namedtuple("Chain", "name DQ QF DOF S DP DS LSE DL")
 
 CA = Chain("a", DQ_A, QF_A, DOF_A, S_A, DP_A, DS_A, LSE_A, DL_A)
 CB = Chain("b", DQ_B, QF_B, DOF_B, S_B, DP_B, DS_B, LSE_B, DL_B)
@@ -120,37 +116,11 @@ def softmax_stream(ch):
     return out
 
 
-def spread(items, ngaps):
-    """Distribute a flat list over ngaps gaps as evenly as possible, keeping the order."""
-    out, n = [], len(items)
-    for g in range(ngaps):
-        out.append(items[g * n // ngaps:(g + 1) * n // ngaps])
-    return out
-
-
 def dma_piece(kind, p, slot, ptrs=None):
     base = {"k": K_BASE, "v": V_BASE, "kt": KT_BASE}[kind] + slot * SLOT + p * 1024
     src = (KTSRC if kind == "kt" else KSRC) + p
     ptr = {"k": sKPU, "v": sVPU, "kt": sKTP}[kind] if ptrs is None else ptrs[kind]
     return (f"s_add_i32 m0, {s(sWOFF)}, {base}", f"global_load_lds_dwordx4 {v(src)}, {sr(ptr, 2)}")
-
-
-def segment(A, mfmas, valu_gaps, lds=None, dma=None, waits=None):
-    lds, dma, waits = lds or {}, dma or {}, waits or {}
-    for g, m in enumerate(mfmas):
-        if g in waits:
-            A.e(waits[g])
-        A.e(m)
-        fill = list(valu_gaps[g]) if g < len(valu_gaps) else []
-        if g in dma:
-            m0w, ld = dma[g]
-            A.e(m0w)
-            A.e(fill.pop(0) if fill else "s_nop 0")
-            A.e(ld)
-        for x in fill:
-            A.e(x)
-        if g in lds:
-            A.e(lds[g])
 
 
 def block_iteration(A, par, kb, first=False, last=False, dma1=None, dma2=None):
@@ -163,7 +133,7 @@ def block_iteration(A, par, kb, first=False, last=False, dma1=None, dma2=None):
     lds = {} if last else {g: read_kv(g, par, kb) for g in range(16)}
     dma = {1 + 3 * i: pc for i, pc in enumerate(dma1 or [])}
     A.c("---- segment 1")
-    segment(A, mf, vg, lds=lds, dma=dma)
+    emit.segment(A, mf, vg, lds=lds, dma=dma)
     if first:
         A.e("s_nop 3")                                      # no DQ gaps behind QK(b, 0): its dP is read by the next VALU
     # ---------------- segment 2: QK(a, j+1), DQ(a, j); SM(b, j); K^T (j) reloads
@@ -177,7 +147,7 @@ def block_iteration(A, par, kb, first=False, last=False, dma1=None, dma2=None):
         lds, waits = {}, {0: "s_waitcnt lgkmcnt(0)"}
     dma = {9 + 3 * i: pc for i, pc in enumerate(dma2 or [])}
     A.c("---- segment 2")
-    segment(A, mf, vg, lds=lds, dma=dma, waits=waits)
+    emit.segment(A, mf, vg, lds=lds, dma=dma, waits=waits)
 
 
 def interval(A, par, first=False, last=False):
@@ -219,59 +189,17 @@ def prologue(A):
         A.e(f"s_mov_b32 {s(reg + 1)}, %[{nm}_hi]")
     for dst, nm in ((sSP2, "sp2"), (sLDO2, "ldo2"), (sCS, "cs"), (sSCALE, "scale"), (sNLOOP, "nloop"), (sS, "seq")):
         A.e(f"s_mov_b32 {s(dst)}, %[{nm}]")
-    lane, w, r, h = v(X), v(X + 1), v(X + 2), v(X + 3)
-    t0, t1, t2 = v(X + 4), v(X + 5), v(X + 6)
-    A.e(f"v_and_b32 {lane}, 63, %[tid]")
-    A.e(f"v_lshrrev_b32 {w}, 6, %[tid]")
-    A.e(f"v_and_b32 {r}, 31, {lane}")
-    A.e(f"v_lshrrev_b32 {h}, 5, {lane}")
-    A.e(f"v_readfirstlane_b32 {s(sW)}, {w}")
-    A.e(f"s_lshl_b32 {s(sWOFF)}, {s(sW)}, 12")
+    L = emit.lane_decode(A, X, s_wave=sW, s_woff=sWOFF, woff_shift=12)         # v[X : X + 6]: lane, w, r, h, t0, t1, t2
+    w, r, h, t1 = L.w, L.r, L.h, L.t1
+    x3 = (v(X + 7), v(X + 8), v(X + 9))
     A.c("K / V fragment read addresses (the forward's K image: MFMA row r reads window row pi(r), chunk (2 ks + h) ^ (row & 15))")
-    pi, xk, pi8 = v(X + 7), v(X + 8), v(X + 9)
-    A.e(f"v_and_b32 {t0}, 0x13, {r}")
-    A.e(f"v_and_b32 {t1}, 4, {r}")
-    A.e(f"v_lshlrev_b32 {t1}, 1, {t1}")
-    A.e(f"v_and_b32 {t2}, 8, {r}")
-    A.e(f"v_lshrrev_b32 {t2}, 1, {t2}")
-    A.e(f"v_or3_b32 {pi}, {t0}, {t1}, {t2}")
-    A.e(f"v_and_b32 {t0}, 15, {pi}")
-    A.e(f"v_xor_b32 {xk}, {h}, {t0}")
-    A.e(f"v_lshlrev_b32 {pi8}, 8, {pi}")
-    for ks in range(8):
-        A.e(f"v_xor_b32 {t0}, {2 * ks}, {xk}")
-        A.e(f"v_lshl_add_u32 {v(KA + ks)}, {t0}, 4, {pi8}")
+    emit.k_image_read_addrs(A, L, KA, x3)
     A.c("K^T fragment read addresses (the forward's V^T image): row d = 32 dt + r, chunk (2 s + h) ^ ((r >> 1) & 7)")
-    yv, r7 = v(X + 7), v(X + 8)
-    A.e(f"v_bfe_u32 {t0}, {r}, 1, 3")
-    A.e(f"v_xor_b32 {yv}, {h}, {t0}")
-    A.e(f"v_lshlrev_b32 {r7}, 7, {r}")
-    A.e(f"v_add_u32 {r7}, {KT_BASE}, {r7}")
-    for si in range(4):
-        A.e(f"v_xor_b32 {t0}, {2 * si}, {yv}")
-        A.e(f"v_lshl_add_u32 {v(KTA + si)}, {t0}, 4, {r7}")
+    emit.vt_image_read_addrs(A, L, KTA, x3, KT_BASE)
     A.c("K / V DMA source offsets: piece p of wave w = window rows 16 w + 4 p + (lane >> 4)")
-    l4, l15, key0 = v(X + 7), v(X + 8), v(X + 9)
-    A.e(f"v_lshrrev_b32 {l4}, 4, {lane}")
-    A.e(f"v_and_b32 {l15}, 15, {lane}")
-    A.e(f"v_lshl_add_u32 {key0}, {w}, 4, {l4}")
-    for p in range(4):
-        A.e(f"v_add_u32 {t0}, {4 * p}, {key0}")
-        A.e(f"v_add_u32 {t1}, {4 * p}, {l4}")
-        A.e(f"v_xor_b32 {t1}, {l15}, {t1}")
-        A.e(f"v_lshlrev_b32 {t1}, 4, {t1}")
-        A.e(f"v_lshl_add_u32 {v(KSRC + p)}, {t0}, 8, {t1}")
+    emit.k_image_dma_offsets(A, L, KSRC, x3)
     A.c("K^T DMA source offsets: piece p of wave w = rows d = 32 w + 8 p + (lane >> 3)")
-    l3, l7, d0 = v(X + 7), v(X + 8), v(X + 9)
-    A.e(f"v_lshrrev_b32 {l3}, 3, {lane}")
-    A.e(f"v_and_b32 {l7}, 7, {lane}")
-    A.e(f"v_lshl_add_u32 {d0}, {w}, 5, {l3}")
-    for p in range(4):
-        A.e(f"v_add_u32 {t0}, {8 * p}, {d0}")
-        A.e(f"v_bfe_u32 {t1}, {t0}, 1, 3")
-        A.e(f"v_xor_b32 {t1}, {l7}, {t1}")
-        A.e(f"v_lshlrev_b32 {t1}, 4, {t1}")
-        A.e(f"v_mad_u32_u24 {v(KTSRC + p)}, {t0}, {s(sSP2)}, {t1}")
+    emit.vt_image_dma_offsets(A, L, KTSRC, x3, sSP2)
     A.c("this lane's query row w * 64 + r (chain b: + 32): Q / dQ offset, dO offset, lse / delta")
     row = v(X + 10)
     A.e(f"v_lshl_add_u32 {row}, {w}, 6, {r}")
@@ -289,20 +217,14 @@ def prologue(A):
     A.e(f"s_add_u32 {s(sKTP)}, {s(sKT)}, 0")
     A.e(f"s_addc_u32 {s(sKTP + 1)}, {s(sKT + 1)}, 0")
     for p in range(4):
-        m0w, ld = dma_piece("kt", p, 0)
-        A.e(m0w)
-        A.e("s_nop 0")
-        A.e(ld)
+        emit.lds_dma(A, dma_piece("kt", p, 0))
     A.e(f"s_mov_b32 {s(sKTT)}, 128")
     for ptr, src in ((sKP, sK), (sVP, sV)):
         A.e(f"s_add_u32 {s(ptr)}, {s(src)}, 8192")                          # window 0 starts at key 32
         A.e(f"s_addc_u32 {s(ptr + 1)}, {s(src + 1)}, 0")
     for kind in ("k", "v"):
         for p in range(4):
-            m0w, ld = dma_piece(kind, p, 0, ptrs={"k": sKP, "v": sVP})
-            A.e(m0w)
-            A.e("s_nop 0")
-            A.e(ld)
+            emit.lds_dma(A, dma_piece(kind, p, 0, ptrs={"k": sKP, "v": sVP}))
     skip = A.new_label("w01")
     A.e(f"s_cmp_lt_u32 {s(sW)}, 2")
     A.e(f"s_cbranch_scc1 {skip}")
@@ -311,10 +233,7 @@ def prologue(A):
         A.e(f"s_subb_u32 {s(ptr + 1)}, {s(src + 1)}, 0")
     for kind in ("k", "v"):
         for p in range(4):
-            m0w, ld = dma_piece(kind, p, 1, ptrs={"k": sKTP, "v": sTP})
-            A.e(m0w)
-            A.e("s_nop 0")
-            A.e(ld)
+            emit.lds_dma(A, dma_piece(kind, p, 1, ptrs={"k": sKTP, "v": sTP}))
     A.label(skip)
     # this wave's row base of the NEXT window to fetch (window 1 = keys 96..159): rows 16 w .. 16 w + 15 of it
     A.e(f"s_lshl_b32 {s(sROW)}, {s(sW)}, 4")
@@ -360,25 +279,8 @@ def epilogue(A):
     A.e("s_nop 7")
     A.e("s_nop 7")
     A.c("================ epilogue: dQ * scale -> bf16, 16-byte stores (lane halves exchanged pairwise)")
-    for ch, boff in ((CA, 0), (CB, 8192)):
-        for dt in range(4):
-            for g in (0, 2):
-                E = X + 8 + 4 * ((dt * 2 + (g >> 1)) & 3)
-                rd = [v(X + 24 + j) for j in range(8)]
-                for j in range(8):
-                    A.e(f"v_accvgpr_read_b32 {rd[j]}, {a(ch.DQ + 16 * dt + 4 * g + j)}")
-                for j in range(8):
-                    A.e(f"v_mul_f32 {rd[j]}, {rd[j]}, {s(sSCALE)}")
-                for j in range(4):
-                    A.e(f"v_cvt_pk_bf16_f32 {v(E + j)}, {rd[2 * j]}, {rd[2 * j + 1]}")
-                A.e("s_nop 1")
-                A.e(f"v_permlane32_swap_b32 {v(E)}, {v(E + 2)}")
-                A.e(f"v_permlane32_swap_b32 {v(E + 1)}, {v(E + 3)}")
-                off = boff + 64 * dt + 16 * g
-                if off < 4096:
-                    A.e(f"global_store_dwordx4 {v(ROWOFF)}, {vr(E, 4)}, {sr(sDQ, 2)} offset:{off}")
-                else:
-                    A.e(f"global_store_dwordx4 {v(X + 7)}, {vr(E, 4)}, {sr(sDQ, 2)} offset:{off - 8192}")
+    for ch, addr in ((CA, ROWOFF), (CB, X + 7)):          # X + 7: chain b's rows, 32 further (generate())
+        emit.store_acc_bf16(A, ch.DQ, s(sSCALE), X + 8, X + 24, v(addr), sDQ)
 
 
 def generate():
@@ -386,26 +288,10 @@ def generate():
     prologue(A)
     A.e(f"v_add_u32 {v(X + 7)}, 8192, {v(ROWOFF)}")     # chain b dQ offset for the epilogue (X + 7 is free from here on)
     interval(A, 0, first=True)
-    A.e(f"s_mov_b32 {s(sLOOP)}, {s(sNLOOP)}")
-    loop, done = A.new_label("loop"), A.new_label("loopdone")
-    A.e(f"s_cmp_eq_u32 {s(sLOOP)}, 0")
-    A.e(f"s_cbranch_scc1 {done}")
-    A.label(loop)
-    interval(A, 1)
-    interval(A, 0)
-    A.e(f"s_sub_u32 {s(sLOOP)}, {s(sLOOP)}, 1")
-    A.e(f"s_cmp_lg_u32 {s(sLOOP)}, 0")
-    A.e(f"s_cbranch_scc1 {loop}")
-    A.label(done)
+    emit.counted_loop(A, sLOOP, sNLOOP, lambda: interval(A, 1), lambda: interval(A, 0))
     interval(A, 1, last=True)
     epilogue(A)
     return A.text()
-
-
-def clobbers():
-    regs = [f"v{i}" for i in range(4, V_LAST + 1)] + [f"a{i}" for i in range(256)] + \
-           [f"s{i}" for i in range(S_FIRST, S_LAST + 1)] + ["vcc", "scc", "memory"]
-    return ", ".join(f'"{x}"' for x in regs)
 
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -413,27 +299,12 @@ OUT_BODY = os.path.join(HERE, "..", "attn_bwd_dq64_body.inc")
 
 
 def render():
-    body = generate()
-    lines = ["// GENERATED by mixgrpo_amd/csrc/gen/attn_bwd_dq64.py -- do not edit; see that file for the design.",
-             "#define ATTN_BWD_DQ64_CLOBBERS " + clobbers(),
-             "#define ATTN_BWD_DQ64_BODY \\"]
-    for ln in body.rstrip("\n").split("\n"):
-        lines.append('  "' + ln.replace("\\", "\\\\").replace('"', '\\"') + '\\n" \\')
-    lines.append('  ""')
-    return "\n".join(lines) + "\n"
+    return emit.render("ATTN_BWD_DQ64", __file__, generate(), emit.clobbers(V_LAST, S_FIRST, S_LAST))
 
 
 def write(path=OUT_BODY):
-    txt = render()
-    old = open(path).read() if os.path.exists(path) else None
-    if old != txt:
-        with open(path, "w") as f:
-            f.write(txt)
-    return path
+    return emit.write_if_changed(path, render())
 
 
 if __name__ == "__main__":
-    if "--print" in sys.argv:
-        sys.stdout.write(generate())
-    else:
-        print(write())
+    emit.main(generate, write)

@@ -32,7 +32,7 @@ its own forced test (tests/test_hip_mmdit.py::test_attention_fwd64_rescale_path)
 The stream is checked on the CPU before it ever runs: tests/asm_emu.py interprets it (4 waves, LDS, waitcnt-visible data)
 against the oracle and a static pass checks the gfx950 software hazards (MFMA result -> VALU read 12 wait states, ...).
 
-Second variant (round 4, `ACC`, attn_fwd64q_body.inc, kernel attn_fwd64q_kernel): for a Q that the producer has ALREADY scaled by
+Second variant (round 4, `acc`, written ACC below, attn_fwd64q_body.inc, kernel attn_fwd64q_kernel): for a Q that the producer has ALREADY scaled by
 c (mgx_qk_norm_rope_fwd's q_scale: one bf16 rounding of q c instead of one of q), with m SUBTRACTED BY THE MATRIX PIPE: from
 the second tile on, the first of a score tile's eight MFMAs takes C = a block of 16 registers holding -m (one block per chain,
 written once when the first tile's maximum is known, moved by the fix-up), so the accumulator comes out as s c - m c and the
@@ -40,11 +40,31 @@ softmax's `v_fma_f32 t, s, c, -mc` -- one of the ~3.5 single-issue instructions 
 at 2552 cycles per iteration against the pipe's 2048 -- disappears: v_exp_f32 reads the accumulator directly.  The first tile
 (scores needed before m exists) still subtracts, with v_sub_f32.
 
+This file holds what is this kernel's own; the emitters it shares with the two backward generators (which are built the
+same way: read this docstring first) are in csrc/gen/emit.py: line buffer, counted loop, lane decode, the K / V^T tile
+images' addresses, the LDS-DMA idiom and `segment`, the store block, the .inc text.  Which stream is generated is an argument
+(`Variant`), never module state.
+
 Run `python mixgrpo_amd/csrc/gen/attn_fwd64.py` to rewrite mixgrpo_amd/csrc/attn_fwd64_body.inc and attn_fwd64q_body.inc
-(build.py does).
+(build.py does); `--diag [--acc] [--timing-only=nodma,nolds,novalu,nobarrier]` writes scratch/attn_fwd64_diag_body.inc.
 """
 import os
 import sys
+from collections import namedtuple
+from dataclasses import dataclass
+
+import emit
+from emit import MFMA, Asm, a, ar, s, sr, v, vr
+
+
+@dataclass(frozen=True)
+class Variant:
+    """Which stream: acc = attn_fwd64q (module docstring); diag = shader-clock stamps, one block (scratch/fwd64_diag.hip);
+    timing_only = diagnostic variants with WRONG results that leave work out: "nodma", "nolds", "novalu", "nobarrier"."""
+    acc: bool = False
+    diag: bool = False
+    timing_only: frozenset = frozenset()
+
 
 # ------------------------------------------------------------------------------------------------ register map
 O_A, O_B = 0, 64          # a: 4 d-tiles x 16
@@ -69,7 +89,6 @@ LOFF = 236
 V_LAST = 239
 NM_A, NM_B = 240, X + 16  # ACC variant: v[240:255] / v[216:231] = 16 x (-m) of chain A / B, the SrcC of a score tile's first MFMA
                           # (X + 16 .. X + 31 is otherwise only the epilogue's staging: dead while the blocks are live)
-ACC = False               # set by generate(acc=True)
 DBG_OFF, DBG_LO = 237, 238   # v237, v[238:239]: diagnostic builds only
 
 # scalars (copied from the asm operands into fixed registers, all clobbered)
@@ -91,62 +110,9 @@ SLOT = 16384
 BIG = "0x53800000"        # 2^40
 
 
-def v(i):
-    return f"v{i}"
-
-
-def vr(i, n):
-    return f"v[{i}:{i + n - 1}]"
-
-
-def a(i):
-    return f"a{i}"
-
-
-def ar(i, n):
-    return f"a[{i}:{i + n - 1}]"
-
-
-def s(i):
-    return f"s{i}"
-
-
-def sr(i, n):
-    return f"s[{i}:{i + n - 1}]"
-
-
-class Chain:
-    def __init__(self, name, O, Q, S, P, M, MC, L, NM):
-        self.name, self.O, self.Q, self.S, self.P, self.M, self.MC, self.L, self.NM = name, O, Q, S, P, M, MC, L, NM
-
-
+Chain = namedtuple("Chain", "name O Q S P M MC L NM")
 CA = Chain("A", O_A, Q_A, S_A, P_A, M_A, MC_A, L_A, NM_A)
 CB = Chain("B", O_B, Q_B, S_B, P_B, M_B, MC_B, L_B, NM_B)
-
-
-class Asm:
-    def __init__(self):
-        self.lines = []
-        self.nlabel = 0
-
-    def e(self, text):
-        self.lines.append("  " + text)
-
-    def c(self, text):
-        self.lines.append("  ; " + text)
-
-    def label(self, name):
-        self.lines.append(f"{name}:")
-
-    def new_label(self, stem):
-        self.nlabel += 1
-        return f".L{stem}_{self.nlabel}_%="
-
-    def text(self):
-        return "\n".join(self.lines) + "\n"
-
-
-MFMA = "v_mfma_f32_32x32x16_bf16"
 
 
 # ------------------------------------------------------------------------------------------------ building blocks
@@ -157,12 +123,12 @@ def mfma_pv(ch, n):
     return f"{MFMA} {o}, {vr(VF + 4 * n, 4)}, {vr(ch.P + 4 * sidx, 4)}, {o}"
 
 
-def mfma_qk(ch, n, first_tile=False):
+def mfma_qk(var, ch, n, first_tile=False):
     """n = 8 kb + ks: S[kb] (+)= K fragment (kb, ks) x Q[ks].  ACC: a tile's first product starts from -m (the chain's NM
     block) instead of 0 -- except in the block's first tile, whose scores define m."""
     kb, ks = n >> 3, n & 7
     sreg = vr(ch.S + 16 * kb, 16)
-    c0 = vr(ch.NM, 16) if (ACC and not first_tile) else "0"
+    c0 = vr(ch.NM, 16) if (var.acc and not first_tile) else "0"
     return f"{MFMA} {sreg}, {ar(KF + 4 * n, 4)}, {ar(ch.Q + 4 * ks, 4)}, {c0 if ks == 0 else sreg}"
 
 
@@ -246,7 +212,7 @@ def block_advance_stores(A):
     A.e(f"s_sub_u32 {s(sLEFT)}, {s(sLEFT)}, 1")
 
 
-def softmax_gaps(ch, ngaps=32, first_tile=False):
+def softmax_gaps(var, ch, ngaps=32, first_tile=False):
     """VALU stream of one chain's tile softmax, as `ngaps` lists (one per MFMA gap) + a tail list.
 
     Element e (0..31) = S register e; fma(e) two gaps before exp(e), the sum one gap after, cvt_pk(k) one gap after the
@@ -256,12 +222,12 @@ def softmax_gaps(ch, ngaps=32, first_tile=False):
         return v(T + (e & 7))
 
     def fma(e):
-        if ACC:
+        if var.acc:
             return f"v_sub_f32 {t(e)}, {v(ch.S + e)}, {v(ch.MC)}" if first_tile else None
         return f"v_fma_f32 {t(e)}, {v(ch.S + e)}, {s(sCS)}, -{v(ch.MC)}"
 
     def exp(e):
-        if ACC and not first_tile:
+        if var.acc and not first_tile:
             return f"v_exp_f32 {t(e)}, {v(ch.S + e)}"
         return f"v_exp_f32 {t(e)}, {t(e)}"
 
@@ -296,82 +262,55 @@ def softmax_gaps(ch, ngaps=32, first_tile=False):
     return gaps, tail
 
 
-def max_prefix(ch):
-    """First tile: m = row maximum of the tile (both lane halves), mc = m * c."""
-    t0, t1 = v(X), v(X + 1)
+def row_max(ch, t0, t1):
+    """t0, t1 = the tile's row maximum in this lane half / in the other one (raw S registers)."""
     out = [f"v_max_f32 {t0}, {v(ch.S)}, {v(ch.S + 1)}"]
     for e in range(2, 32, 2):
         out.append(f"v_max3_f32 {t0}, {t0}, {v(ch.S + e)}, {v(ch.S + e + 1)}")
-    out += [f"v_mov_b32 {t1}, {t0}", "s_nop 1", f"v_permlane32_swap_b32 {t0}, {t1}",
-            f"v_max_f32 {v(ch.M)}, {t0}, {t1}",
-            f"v_mov_b32 {v(ch.MC)}, {v(ch.M)}" if ACC else f"v_mul_f32 {v(ch.MC)}, {v(ch.M)}, {s(sCS)}"]
-    if ACC:                                  # (scores are exponents already: mc == m) the SrcC block of every later score tile
-        out += [f"v_sub_f32 {v(ch.NM + j)}, 0, {v(ch.M)}" for j in range(16)]
-    return out
+    return out + [f"v_mov_b32 {t1}, {t0}", "s_nop 1", f"v_permlane32_swap_b32 {t0}, {t1}"]
 
 
-def fixup(A, ch, back):
+def minus_m_block(ch):
+    """ACC: the SrcC block of every later score tile of the chain."""
+    return [f"v_sub_f32 {v(ch.NM + j)}, 0, {v(ch.M)}" for j in range(16)]
+
+
+def max_prefix(var, ch):
+    """First tile: m = row maximum of the tile (both lane halves), mc = m * c."""
+    t0, t1 = v(X), v(X + 1)
+    out = row_max(ch, t0, t1) + [f"v_max_f32 {v(ch.M)}, {t0}, {t1}"]
+    if var.acc:                              # scores are exponents already: mc == m
+        return out + [f"v_mov_b32 {v(ch.MC)}, {v(ch.M)}"] + minus_m_block(ch)
+    return out + [f"v_mul_f32 {v(ch.MC)}, {v(ch.M)}, {s(sCS)}"]
+
+
+def fixup(A, var, ch, back):
     """Out-of-line: some row sum of the tile exceeded 2^40.  New maximum from the (intact) S registers, O and l rescaled
-    exactly once, the tile's P and row sums redone.  Not scheduled: it practically never runs."""
-    t0, t1, al = v(X), v(X + 1), v(X + 2)
-    A.e("s_nop 7")
-    A.e("s_nop 7")                                          # every MFMA that wrote O / S of this chain has retired
-    if ACC:
-        return fixup_acc(A, ch, back)
-    A.e(f"v_max_f32 {t0}, {v(ch.S)}, {v(ch.S + 1)}")
-    for e in range(2, 32, 2):
-        A.e(f"v_max3_f32 {t0}, {t0}, {v(ch.S + e)}, {v(ch.S + e + 1)}")
-    A.e(f"v_mov_b32 {t1}, {t0}")
-    A.e("s_nop 1")
-    A.e(f"v_permlane32_swap_b32 {t0}, {t1}")
-    A.e(f"v_max3_f32 {t0}, {t0}, {t1}, {v(ch.M)}")          # m_new
-    A.e(f"v_sub_f32 {t1}, {v(ch.M)}, {t0}")
-    A.e(f"v_mul_f32 {t1}, {t1}, {s(sCS)}")
-    A.e(f"v_exp_f32 {al}, {t1}")                            # alpha = 2^((m - m_new) c)
-    A.e(f"v_mov_b32 {v(ch.M)}, {t0}")
-    A.e(f"v_mul_f32 {v(ch.MC)}, {t0}, {s(sCS)}")
-    A.e(f"v_mul_f32 {v(ch.L)}, {v(ch.L)}, {al}")
-    for blk in range(0, 64, 8):
-        for j in range(8):
-            A.e(f"v_accvgpr_read_b32 {v(X + 8 + j)}, {a(ch.O + blk + j)}")
-        for j in range(8):
-            A.e(f"v_mul_f32 {v(X + 8 + j)}, {v(X + 8 + j)}, {al}")
-        for j in range(8):
-            A.e(f"v_accvgpr_write_b32 {a(ch.O + blk + j)}, {v(X + 8 + j)}")
-    for k in range(16):                                     # P and row sums again, at the new maximum
-        ta, tb = v(X + 8), v(X + 9)
-        A.e(f"v_fma_f32 {ta}, {v(ch.S + 2 * k)}, {s(sCS)}, -{v(ch.MC)}")
-        A.e(f"v_fma_f32 {tb}, {v(ch.S + 2 * k + 1)}, {s(sCS)}, -{v(ch.MC)}")
-        A.e(f"v_exp_f32 {ta}, {ta}")
-        A.e(f"v_exp_f32 {tb}, {tb}")
-        A.e("s_nop 0")
-        if k == 0:
-            A.e(f"v_add_f32 {v(PS0)}, {ta}, {tb}")
-        else:
-            A.e(f"v_add_f32 {v(PS0)}, {v(PS0)}, {ta}")
-            A.e(f"v_add_f32 {v(PS0)}, {v(PS0)}, {tb}")
-        A.e(f"v_cvt_pk_bf16_f32 {v(ch.P + k)}, {ta}, {tb}")
-    A.e("s_nop 7")                                          # accvgpr / P writes -> the next MFMAs
-    A.e(f"s_branch {back}")
+    exactly once, the tile's P and row sums redone.  Not scheduled: it practically never runs.
 
-
-def fixup_acc(A, ch, back):
-    """ACC variant: the S registers hold s - m already, so r = max(0, row maximum of S) is how far m moves: alpha = 2^-r,
+    ACC: the S registers hold s - m already, so r = max(0, row maximum of S) is how far m moves: alpha = 2^-r,
     P = 2^(S - r), m += r, the -m block -= r (the chain's next score tile is issued after this returns)."""
     t0, t1, al = v(X), v(X + 1), v(X + 2)
-    A.e(f"v_max_f32 {t0}, {v(ch.S)}, {v(ch.S + 1)}")
-    for e in range(2, 32, 2):
-        A.e(f"v_max3_f32 {t0}, {t0}, {v(ch.S + e)}, {v(ch.S + e + 1)}")
-    A.e(f"v_mov_b32 {t1}, {t0}")
-    A.e("s_nop 1")
-    A.e(f"v_permlane32_swap_b32 {t0}, {t1}")
-    A.e(f"v_max3_f32 {t0}, {t0}, {t1}, 0")                  # r
-    A.e(f"v_sub_f32 {t1}, 0, {t0}")
-    A.e(f"v_exp_f32 {al}, {t1}")                            # alpha = 2^-r
-    A.e(f"v_add_f32 {v(ch.M)}, {v(ch.M)}, {t0}")
-    A.e(f"v_mov_b32 {v(ch.MC)}, {v(ch.M)}")
-    for j in range(16):
-        A.e(f"v_sub_f32 {v(ch.NM + j)}, 0, {v(ch.M)}")
+    ta, tb = v(X + 8), v(X + 9)
+    A.e("s_nop 7")
+    A.e("s_nop 7")                                          # every MFMA that wrote O / S of this chain has retired
+    for x in row_max(ch, t0, t1):
+        A.e(x)
+    if var.acc:
+        A.e(f"v_max3_f32 {t0}, {t0}, {t1}, 0")              # r
+        A.e(f"v_sub_f32 {t1}, 0, {t0}")
+        A.e(f"v_exp_f32 {al}, {t1}")                        # alpha = 2^-r
+        A.e(f"v_add_f32 {v(ch.M)}, {v(ch.M)}, {t0}")
+        A.e(f"v_mov_b32 {v(ch.MC)}, {v(ch.M)}")
+        for x in minus_m_block(ch):
+            A.e(x)
+    else:
+        A.e(f"v_max3_f32 {t0}, {t0}, {t1}, {v(ch.M)}")      # m_new
+        A.e(f"v_sub_f32 {t1}, {v(ch.M)}, {t0}")
+        A.e(f"v_mul_f32 {t1}, {t1}, {s(sCS)}")
+        A.e(f"v_exp_f32 {al}, {t1}")                        # alpha = 2^((m - m_new) c)
+        A.e(f"v_mov_b32 {v(ch.M)}, {t0}")
+        A.e(f"v_mul_f32 {v(ch.MC)}, {t0}, {s(sCS)}")
     A.e(f"v_mul_f32 {v(ch.L)}, {v(ch.L)}, {al}")
     for blk in range(0, 64, 8):
         for j in range(8):
@@ -381,9 +320,11 @@ def fixup_acc(A, ch, back):
         for j in range(8):
             A.e(f"v_accvgpr_write_b32 {a(ch.O + blk + j)}, {v(X + 8 + j)}")
     for k in range(16):                                     # P and row sums again, at the new maximum
-        ta, tb = v(X + 8), v(X + 9)
-        A.e(f"v_sub_f32 {ta}, {v(ch.S + 2 * k)}, {t0}")
-        A.e(f"v_sub_f32 {tb}, {v(ch.S + 2 * k + 1)}, {t0}")
+        for tx, e in ((ta, 2 * k), (tb, 2 * k + 1)):
+            if var.acc:
+                A.e(f"v_sub_f32 {tx}, {v(ch.S + e)}, {t0}")
+            else:
+                A.e(f"v_fma_f32 {tx}, {v(ch.S + e)}, {s(sCS)}, -{v(ch.MC)}")
         A.e(f"v_exp_f32 {ta}, {ta}")
         A.e(f"v_exp_f32 {tb}, {tb}")
         A.e("s_nop 0")
@@ -397,55 +338,16 @@ def fixup_acc(A, ch, back):
     A.e(f"s_branch {back}")
 
 
-TIMING_ONLY = set()        # diagnostic variants (wrong results; scratch harness only): "nodma", "nolds", "novalu", "nobarrier"
-
-
-def segment(A, mfmas, valu_gaps, valu_tail, lds=None, dma=None, pre=None, waits=None, extra=None):
-    """Emit one segment: per gap [wait] MFMA, the gap's VALU slice, at most one LDS read, at most one DMA piece.
-
-    lds: {gap: instr}; dma: {gap: (m0 write, load)}; waits: {gap: 's_waitcnt ...'} placed in front of the gap's MFMA."""
-    lds, dma, waits, extra = lds or {}, dma or {}, waits or {}, extra or {}
-    if "nodma" in TIMING_ONLY:
-        dma = {}
-    if "nolds" in TIMING_ONLY:
-        lds = {}
-    if "novalu" in TIMING_ONLY:
-        valu_gaps = [[] for _ in valu_gaps]
-    for x in pre or []:
-        A.e(x)
-    for g, m in enumerate(mfmas):
-        if g in waits:
-            A.e(waits[g])
-        A.e(m)
-        fill = list(valu_gaps[g]) if g < len(valu_gaps) else []
-        if g in dma:
-            m0w, ld = dma[g]
-            A.e(m0w)
-            if fill:
-                A.e(fill.pop(0))           # one VALU between the m0 write and the DMA (the required wait state)
-            else:
-                A.e("s_nop 0")
-            A.e(ld)
-        for x in fill:
-            A.e(x)
-        if g in lds:
-            A.e(lds[g])
-        for x in extra.get(g, []):
-            A.e(x)
-    for x in valu_tail:
-        A.e(x)
-
-
-def iteration(A, par, fixups, first=False, last=False):
+def iteration(A, var, par, fixups, first=False, last=False):
     """One K/V tile i with i & 1 == par.  Slots: K(j), V(j) live in slot j & 1."""
     A.c(f"================ iteration parity {par}{' FIRST' if first else ''}{' LAST' if last else ''}")
     # ---------------- segment 1: MFMA chain B (P V of tile i-1, S^T of tile i), softmax chain A
-    mf = ([] if first else [mfma_pv(CB, n) for n in range(16)]) + [mfma_qk(CB, n, first_tile=first) for n in range(16)]
+    mf = ([] if first else [mfma_pv(CB, n) for n in range(16)]) + [mfma_qk(var, CB, n, first_tile=first) for n in range(16)]
     ng = len(mf)
-    vg, vt = softmax_gaps(CA, ng, first_tile=first)
+    vg, vt = softmax_gaps(var, CA, ng, first_tile=first)
     pre = []
     if first:
-        pre = max_prefix(CA)
+        pre = max_prefix(var, CA)
     dma, lds, extra1, extra2 = {}, {}, {}, {}
     if last:
         # the NEXT block's first tiles and Q fragments (the same block again when this is the workgroup's last: unused):
@@ -469,12 +371,12 @@ def iteration(A, par, fixups, first=False, last=False):
     for n in range(16):
         lds[(n if first else 8 + n)] = ds_read_v(n, par)
     A.c("---- segment 1")
-    segment(A, mf, vg, vt, lds=lds, dma=dma, pre=pre, extra=extra1)
+    emit.segment(A, mf, vg, vt, lds=lds, dma=dma, pre=pre, extra=extra1, timing_only=var.timing_only)
     end_of_softmax(A, CA, fixups, first)
     # ---------------- segment 2: MFMA chain A (P V of tile i, S^T of tile i+1), softmax chain B
-    mf = [mfma_pv(CA, n) for n in range(16)] + ([] if last else [mfma_qk(CA, n) for n in range(16)])
-    vg, vt = softmax_gaps(CB, 32 if not last else 16, first_tile=first)
-    pre = max_prefix(CB) if first else []
+    mf = [mfma_pv(CA, n) for n in range(16)] + ([] if last else [mfma_qk(var, CA, n) for n in range(16)])
+    vg, vt = softmax_gaps(var, CB, 32 if not last else 16, first_tile=first)
+    pre = max_prefix(var, CB) if first else []
     lds, waits = {}, {0: "s_waitcnt lgkmcnt(0)"}            # every V^T fragment of the tile has landed
     if not last:
         for n in range(16):
@@ -482,11 +384,11 @@ def iteration(A, par, fixups, first=False, last=False):
         waits[16] = "s_waitcnt lgkmcnt(8)"
         waits[24] = "s_waitcnt lgkmcnt(0)"
     A.c("---- segment 2")
-    segment(A, mf, vg, vt, lds=lds, pre=pre, waits=waits, extra=extra2)
+    emit.segment(A, mf, vg, vt, lds=lds, pre=pre, waits=waits, extra=extra2, timing_only=var.timing_only)
     end_of_softmax(A, CB, fixups, first)
     if not last:
         A.e("s_waitcnt vmcnt(0)")                           # this iteration's K(i+2), V^T(i+1) pieces
-        if "nobarrier" not in TIMING_ONLY:
+        if "nobarrier" not in var.timing_only:
             A.e("s_barrier")
 
 
@@ -509,62 +411,20 @@ def prologue(A):
                       (sO, "o_lo"), (sO + 1, "o_hi"), (sL, "l_lo"), (sL + 1, "l_hi"), (sSP2, "sp2"), (sLDO2, "ldo2"),
                       (sCS, "cs"), (sNLOOP, "nloop"), (sKMAX, "kmax"), (sVMAX, "vmax")):
         A.e(f"s_mov_b32 {s(dst)}, %[{name}]")
-    lane, w, r, h = v(X), v(X + 1), v(X + 2), v(X + 3)
-    t0, t1, t2 = v(X + 4), v(X + 5), v(X + 6)
-    A.e(f"v_and_b32 {lane}, 63, %[tid]")
-    A.e(f"v_lshrrev_b32 {w}, 6, %[tid]")
-    A.e(f"v_and_b32 {r}, 31, {lane}")
-    A.e(f"v_lshrrev_b32 {h}, 5, {lane}")
-    A.e(f"v_readfirstlane_b32 {s(sW)}, {w}")
-    A.e(f"s_lshl_b32 {s(sWOFF)}, {s(sW)}, 12")
+    L = emit.lane_decode(A, X, s_wave=sW, s_woff=sWOFF, woff_shift=12)         # v[X : X + 6]: lane, w, r, h, t0, t1, t2
+    w, r, h, t0, t1 = L.w, L.r, L.h, L.t0, L.t1
+    x3 = (v(X + 7), v(X + 8), v(X + 9))
     A.c("K fragment read addresses: MFMA row r reads tile row pi(r) (bits 2 and 3 of r exchanged), so that the S^T")
     A.c("accumulator's rows are keys 16 s + 8 h + j, the plain V^T chunk order")
-    pi, xk, pi8 = v(X + 7), v(X + 8), v(X + 9)
-    A.e(f"v_and_b32 {t0}, 0x13, {r}")
-    A.e(f"v_and_b32 {t1}, 4, {r}")
-    A.e(f"v_lshlrev_b32 {t1}, 1, {t1}")
-    A.e(f"v_and_b32 {t2}, 8, {r}")
-    A.e(f"v_lshrrev_b32 {t2}, 1, {t2}")
-    A.e(f"v_or3_b32 {pi}, {t0}, {t1}, {t2}")
-    A.e(f"v_and_b32 {t0}, 15, {pi}")
-    A.e(f"v_xor_b32 {xk}, {h}, {t0}")
-    A.e(f"v_lshlrev_b32 {pi8}, 8, {pi}")
-    for ks in range(8):
-        A.e(f"v_xor_b32 {t0}, {2 * ks}, {xk}")
-        A.e(f"v_lshl_add_u32 {v(KA + ks)}, {t0}, 4, {pi8}")
+    emit.k_image_read_addrs(A, L, KA, x3)
     A.c("V^T fragment read addresses: row d = 32 dt + r, chunk (2 s + h) ^ ((r >> 1) & 7)")
-    yv, r7 = v(X + 7), v(X + 8)
-    A.e(f"v_bfe_u32 {t0}, {r}, 1, 3")
-    A.e(f"v_xor_b32 {yv}, {h}, {t0}")
-    A.e(f"v_lshlrev_b32 {r7}, 7, {r}")
-    A.e(f"v_add_u32 {r7}, {V_BASE}, {r7}")
-    for si in range(4):
-        A.e(f"v_xor_b32 {t0}, {2 * si}, {yv}")
-        A.e(f"v_lshl_add_u32 {v(VA + si)}, {t0}, 4, {r7}")
+    emit.vt_image_read_addrs(A, L, VA, x3, V_BASE)
     A.c("K DMA source offsets: piece p of wave w = keys 16 w + 4 p + (lane >> 4), LDS position lane & 15 holds chunk")
     A.c("(lane & 15) ^ (key & 15)")
-    l4, l15, key0 = v(X + 7), v(X + 8), v(X + 9)
-    A.e(f"v_lshrrev_b32 {l4}, 4, {lane}")
-    A.e(f"v_and_b32 {l15}, 15, {lane}")
-    A.e(f"v_lshl_add_u32 {key0}, {w}, 4, {l4}")
-    for p in range(4):
-        A.e(f"v_add_u32 {t0}, {4 * p}, {key0}")
-        A.e(f"v_add_u32 {t1}, {4 * p}, {l4}")
-        A.e(f"v_xor_b32 {t1}, {l15}, {t1}")
-        A.e(f"v_lshlrev_b32 {t1}, 4, {t1}")
-        A.e(f"v_lshl_add_u32 {v(KS + p)}, {t0}, 8, {t1}")
+    emit.k_image_dma_offsets(A, L, KS, x3)
     A.c("V^T DMA source offsets: piece p of wave w = rows d = 32 w + 8 p + (lane >> 3), position lane & 7 holds chunk")
     A.c("(lane & 7) ^ ((d >> 1) & 7)")
-    l3, l7, d0 = v(X + 7), v(X + 8), v(X + 9)
-    A.e(f"v_lshrrev_b32 {l3}, 3, {lane}")
-    A.e(f"v_and_b32 {l7}, 7, {lane}")
-    A.e(f"v_lshl_add_u32 {d0}, {w}, 5, {l3}")
-    for p in range(4):
-        A.e(f"v_add_u32 {t0}, {8 * p}, {d0}")
-        A.e(f"v_bfe_u32 {t1}, {t0}, 1, 3")
-        A.e(f"v_xor_b32 {t1}, {l7}, {t1}")
-        A.e(f"v_lshlrev_b32 {t1}, 4, {t1}")
-        A.e(f"v_mad_u32_u24 {v(VS + p)}, {t0}, {s(sSP2)}, {t1}")
+    emit.vt_image_dma_offsets(A, L, VS, x3, sSP2)
     A.c("Q / O / lse offsets of this lane's query row w * 64 + r (chain B: + 32 rows)")
     A.e(f"v_lshl_add_u32 {t0}, {w}, 6, {r}")
     A.e(f"v_lshlrev_b32 {t1}, 8, {t0}")
@@ -587,9 +447,7 @@ def prologue(A):
         A.e(x)
     for pc in ([dma_piece("k", p, 0) for p in range(4)] + [dma_piece("v", p, 0) for p in range(4)] +
                [dma_piece("k", p, 1, ptr=sRET) for p in range(4)]):
-        A.e(pc[0])
-        A.e("s_nop 0")
-        A.e(pc[1])
+        emit.lds_dma(A, pc)
     A.c("Q fragments (B operand of S^T = K Q^T): Q[row][16 ks + 8 h ..]")
     for ch, off in ((CA, QOFF_A), (CB, QOFF_B)):
         for ks in range(8):
@@ -597,7 +455,7 @@ def prologue(A):
     A.e("s_waitcnt vmcnt(0)")
 
 
-def block_start(A):
+def block_start(A, var):
     """Every block: O = 0, the block's first tiles (fetched during the previous block's last iteration, or by the prologue)
     have landed -- the previous block's O / lse stores, the youngest entries of the vector-memory queue, stay in flight --,
     K(0) fragments, S^T of chain A."""
@@ -618,7 +476,7 @@ def block_start(A):
     A.e("s_waitcnt lgkmcnt(0)")
     A.e("s_barrier")                                 # every wave holds K(0): slot 0 may be refilled with K(2)
     for n in range(16):
-        A.e(mfma_qk(CA, n, first_tile=True))
+        A.e(mfma_qk(var, CA, n, first_tile=True))
     A.e("s_nop 7")
     A.e("s_nop 7")
 
@@ -649,26 +507,13 @@ def epilogue(A):
         A.e(f"global_store_dword {v(LOFF)}, {tmp}, {sr(sL, 2)} offset:{4 * lrow}")
         A.e("s_mov_b64 exec, -1")
         A.label(skip)
-        for dt in range(4):
-            for g in (0, 2):
-                E = X + 8 + 4 * ((dt * 2 + (g >> 1)) & 3)           # four staging quads in rotation
-                rd = [v(X + 24 + j) for j in range(8)]
-                for j in range(8):
-                    A.e(f"v_accvgpr_read_b32 {rd[j]}, {a(ch.O + 16 * dt + 4 * g + j)}")
-                for j in range(8):
-                    A.e(f"v_mul_f32 {rd[j]}, {rd[j]}, {inv}")
-                for j in range(4):
-                    A.e(f"v_cvt_pk_bf16_f32 {v(E + j)}, {rd[2 * j]}, {rd[2 * j + 1]}")
-                A.e("s_nop 1")
-                A.e(f"v_permlane32_swap_b32 {v(E)}, {v(E + 2)}")
-                A.e(f"v_permlane32_swap_b32 {v(E + 1)}, {v(E + 3)}")
-                A.e(f"global_store_dwordx4 {v(ooff)}, {vr(E, 4)}, {sr(sO, 2)} offset:{64 * dt + 16 * g}")
+        emit.store_acc_bf16(A, ch.O, inv, X + 8, X + 24, v(ooff), sO)      # four staging quads, eight read registers
     # (no vmcnt(0): the wave ends with its stores in flight, the CU takes the next workgroup meanwhile)
 
 
-def stamp(A, k):
+def stamp(A, k, clock="s_memtime"):
     """Diagnostic builds only (scratch/fwd64_diag.hip): shader-clock stamp k of this wave into the debug buffer."""
-    A.e(f"s_memtime {sr(sRET, 2)}")
+    A.e(f"{clock} {sr(sRET, 2)}")
     A.e("s_waitcnt lgkmcnt(0)")
     A.e(f"v_mov_b32 {v(DBG_LO)}, {s(sRET)}")
     A.e(f"v_mov_b32 {v(DBG_LO + 1)}, {s(sRET + 1)}")
@@ -677,19 +522,11 @@ def stamp(A, k):
     A.e("s_mov_b64 exec, -1")
 
 
-def generate(diag=False, acc=False):
-    global ACC
-    ACC = acc
-    try:
-        return _generate(diag)
-    finally:
-        ACC = False
-
-
-def _generate(diag):
+def generate(diag=False, acc=False, timing_only=()):
+    var = Variant(acc=acc, diag=diag, timing_only=frozenset(timing_only))
     A = Asm()
     fixups = []
-    if diag:
+    if var.diag:
         A.e(f"s_mov_b32 {s(sDBG)}, %[d_lo]")
         A.e(f"s_mov_b32 {s(sDBG + 1)}, %[d_hi]")
         A.e(f"v_lshrrev_b32 {v(DBG_OFF)}, 6, %[tid]")
@@ -698,39 +535,23 @@ def _generate(diag):
     prologue(A)
     block = A.new_label("block")
     A.label(block)
-    block_start(A)
-    if diag:
+    block_start(A, var)
+    if var.diag:
         stamp(A, 1)
-    iteration(A, 0, fixups, first=True)
-    if diag:
+    iteration(A, var, 0, fixups, first=True)
+    if var.diag:
         stamp(A, 2)
-    A.e(f"s_mov_b32 {s(sLOOP)}, {s(sNLOOP)}")
-    loop, done = A.new_label("loop"), A.new_label("loopdone")
-    A.e(f"s_cmp_eq_u32 {s(sLOOP)}, 0")
-    A.e(f"s_cbranch_scc1 {done}")
-    A.label(loop)
-    iteration(A, 1, fixups)
-    iteration(A, 0, fixups)
-    A.e(f"s_sub_u32 {s(sLOOP)}, {s(sLOOP)}, 1")
-    A.e(f"s_cmp_lg_u32 {s(sLOOP)}, 0")
-    A.e(f"s_cbranch_scc1 {loop}")
-    A.label(done)
-    if diag:
+    emit.counted_loop(A, sLOOP, sNLOOP, lambda: iteration(A, var, 1, fixups), lambda: iteration(A, var, 0, fixups))
+    if var.diag:
         stamp(A, 3)
-    iteration(A, 1, fixups, last=True)
-    if diag:
+    iteration(A, var, 1, fixups, last=True)
+    if var.diag:
         stamp(A, 4)
     epilogue(A)
     block_advance_stores(A)
-    if diag:
+    if var.diag:                                                        # one block only; wall clock behind the six stamps
         stamp(A, 5)
-        A.e(f"s_memrealtime {sr(sRET, 2)}")
-        A.e("s_waitcnt lgkmcnt(0)")
-        A.e(f"v_mov_b32 {v(DBG_LO)}, {s(sRET)}")
-        A.e(f"v_mov_b32 {v(DBG_LO + 1)}, {s(sRET + 1)}")
-        A.e("s_mov_b64 exec, 1")
-        A.e(f"global_store_dwordx2 {v(DBG_OFF)}, {vr(DBG_LO, 2)}, {sr(sDBG, 2)} offset:48")
-        A.e("s_mov_b64 exec, -1")
+        stamp(A, 6, clock="s_memrealtime")
         A.e("s_waitcnt vmcnt(0)")
     else:
         A.e(f"s_cmp_lg_u32 {s(sLEFT)}, 0")
@@ -740,15 +561,9 @@ def _generate(diag):
     A.c("================ out-of-line rescale fix-ups")
     for fix, back, ch in fixups:
         A.label(fix)
-        fixup(A, ch, back)
+        fixup(A, var, ch, back)
     A.label(end)
     return A.text()
-
-
-def clobbers(acc=False):
-    regs = [f"v{i}" for i in range(4, (255 if acc else V_LAST) + 1)] + [f"a{i}" for i in range(256)] + \
-           [f"s{i}" for i in range(S_FIRST, S_LAST + 1)] + ["vcc", "scc", "memory"]
-    return ", ".join(f'"{x}"' for x in regs)
 
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -756,38 +571,23 @@ OUT_BODY = os.path.join(HERE, "..", "attn_fwd64_body.inc")
 OUT_BODY_Q = os.path.join(HERE, "..", "attn_fwd64q_body.inc")
 
 
-def render(diag=False, acc=False):
-    body = generate(diag, acc)
-    name = "ATTN_FWD64Q" if acc else "ATTN_FWD64"
-    lines = ["// GENERATED by mixgrpo_amd/csrc/gen/attn_fwd64.py -- do not edit; see that file for the design.",
-             f"#define {name}_CLOBBERS " + clobbers(acc),
-             f"#define {name}_BODY \\"]
-    for ln in body.rstrip("\n").split("\n"):
-        lines.append('  "' + ln.replace("\\", "\\\\").replace('"', '\\"') + '\\n" \\')
-    lines.append('  ""')
-    return "\n".join(lines) + "\n"
+def render(diag=False, acc=False, timing_only=()):
+    # ACC: v[240:255] hold chain A's -m block
+    return emit.render("ATTN_FWD64Q" if acc else "ATTN_FWD64", __file__, generate(diag, acc, timing_only),
+                       emit.clobbers(255 if acc else V_LAST, S_FIRST, S_LAST))
 
 
 def write():
-    for path, acc in ((OUT_BODY, False), (OUT_BODY_Q, True)):
-        txt = render(acc=acc)
-        old = open(path).read() if os.path.exists(path) else None
-        if old != txt:
-            with open(path, "w") as f:
-                f.write(txt)
-    return OUT_BODY, OUT_BODY_Q
+    return tuple(emit.write_if_changed(path, render(acc=acc)) for path, acc in ((OUT_BODY, False), (OUT_BODY_Q, True)))
 
 
 if __name__ == "__main__":
-    if "--print" in sys.argv:
-        sys.stdout.write(generate("--diag" in sys.argv, "--acc" in sys.argv))
-    elif "--diag" in sys.argv:                      # scratch/fwd64_diag.hip includes this one
-        for a_ in sys.argv:
-            if a_.startswith("--timing-only="):
-                TIMING_ONLY.update(a_.split("=")[1].split(","))
+    acc = "--acc" in sys.argv
+    timing = [x for a_ in sys.argv if a_.startswith("--timing-only=") for x in a_.split("=")[1].split(",")]
+    if "--diag" in sys.argv and "--print" not in sys.argv:      # scratch/fwd64_diag.hip includes this one
         out = os.path.join(HERE, "..", "..", "..", "scratch", "attn_fwd64_diag_body.inc")
         with open(out, "w") as f:
-            f.write(render(diag=True, acc="--acc" in sys.argv))
+            f.write(render(diag=True, acc=acc, timing_only=timing))
         print(out)
     else:
-        print(write())
+        emit.main(lambda: generate("--diag" in sys.argv, acc, timing), write)

@@ -115,6 +115,23 @@ def test_static_hazards_clean(acc):
     assert text.count("v_mfma_f32_32x32x16_bf16") == 256
 
 
+@ACC
+@pytest.mark.parametrize("switch", [None, "nodma", "nolds", "novalu", "nobarrier"])
+def test_diagnostic_variants_generate_and_leave_no_state(acc, switch):
+    """The stamped (--diag) stream and its timing-only variants (scratch/fwd64_stamps.py; wrong results by construction, so
+    not interpreted): each still parses, holds the block's 256 MFMAs and is hazard-clean -- and, a variant being an argument
+    and not module state, generating one leaves the shipped stream of generate(acc=...) as it was."""
+    before = G.generate(acc=acc)
+    text = G.generate(diag=True, acc=acc, timing_only=[switch] if switch else [])
+    insts, labels = asm_emu.parse(text)
+    assert insts and any(k.startswith(".Lloop_") for k in labels)
+    assert text.count("s_memtime") == 6 and "s_memtime" not in before
+    assert text != G.generate(diag=True, acc=acc, timing_only=[]) or switch is None
+    assert text.count("v_mfma_f32_32x32x16_bf16") == 256
+    assert asm_emu.check_hazards(text) == []
+    assert G.generate(acc=acc) == before and G.generate(acc=not acc) != before
+
+
 def test_hazard_checker_sees_a_planted_hazard():
     bad = "v_mfma_f32_32x32x16_bf16 v[4:19], a[0:3], a[4:7], 0\nv_add_f32 v40, v4, v5\n"
     assert any(x.startswith("R1") for x in asm_emu.check_hazards(bad))
