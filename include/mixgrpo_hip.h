@@ -269,6 +269,23 @@ int mgx_attn_fwd_log2(const uint16_t* Q2, const uint16_t* K, const uint16_t* Vt,
 int mgx_attn_fwd_path(int B, int H, int S, int Sp, long ldo, long o_bstride);
 int mgx_attn_bwd_path(int B, int H, int S, int Sp, long ldo, long o_bstride);
 
+/* mgx_attn_fwd_log2 with a masked key tail, for a sequence padded to a multiple of 256 so that the 64-query kernel (and the
+ * fused projections in front of it) apply: the no-grad F.scaled_dot_product_attention of the rollout,
+ * fastvideo/utils/sampling_utils.py:68-82, at resolutions whose token count is off 256 (720 x 720: 512 + 2025 = 2537 -> 2560).
+ * Everything is allocated at Sa, Sa % 256 == 0: Q2, K [B,H,Sa,128], Vt [B,H,128,Sa], O with Sa rows per batch
+ * (o_bstride >= Sa * ldo), lse [B,H,Sa] (optional).  Sa - 256 < kv_len <= Sa.  Rows of Q2 / K and columns of Vt >= kv_len may
+ * hold ANY FINITE values: such keys get probability exactly 0 (their score is replaced by -inf before the softmax), and the
+ * padding rows of Q2 are not read at all.  Queries are not masked: rows < kv_len of O and lse are softmax attention over the
+ * keys 0 .. kv_len - 1 only (lse the natural logarithm over those keys) and do not depend on the padding by a bit; rows
+ * >= kv_len are written with unspecified finite values (today: those of row kv_len - 1).  kv_len == Sa gives the bits of
+ * mgx_attn_fwd_log2.  Forward only: the backward has no masked tail yet.
+ * Returns 1 and launches NOTHING when the 64-query kernel cannot take the problem -- mgx_attn_fwd_path(B, H, Sa, Sa, ..) is 0
+ * (the persistent walk, Sa % 256, the offset fields, MGX_ATTN_W64=0) or kv_len is out of range: the caller keeps its unpadded
+ * path, as with mgx_linear_qk_norm_rope.  mgx_attn_fwd_kv_path is that predicate (1 = taken, 0 = refused), launches nothing. */
+int mgx_attn_fwd_log2_kv(const uint16_t* Q2, const uint16_t* K, const uint16_t* Vt, uint16_t* O, float* lse, int B, int H,
+                         int Sa, int kv_len, long ldo, long o_bstride, void* stream);
+int mgx_attn_fwd_kv_path(int B, int H, int Sa, int kv_len, long ldo, long o_bstride);
+
 /* fp8 (OCP e4m3) variant of mgx_attn_fwd: the "fp8 MFMA attention path" of BASELINE.json configs[4].  The reference
  * has no fp8 attention; the entry points serve the same SDPA call sites (fastvideo/utils/sampling_utils.py:68-82,
  * train_grpo_flux.py:134-144).

@@ -74,6 +74,8 @@ SIGNATURES = {
     "mgx_attn_fwd": (_I, [_P] * 5 + [_I] * 4 + [_L, _L, _F, _P]),
     "mgx_attn_fwd_log2": (_I, [_P] * 5 + [_I] * 4 + [_L, _L, _P]),
     "mgx_attn_fwd_path": (_I, [_I] * 4 + [_L, _L]),
+    "mgx_attn_fwd_log2_kv": (_I, [_P] * 5 + [_I] * 4 + [_L, _L, _P]),
+    "mgx_attn_fwd_kv_path": (_I, [_I] * 4 + [_L, _L]),
     "mgx_attn_bwd_path": (_I, [_I] * 4 + [_L, _L]),
     "mgx_attn_fp8_quantize": (_I, [_P] * 7 + [_I] * 4 + [_P]),
     "mgx_attn_fwd_fp8": (_I, [_P] * 6 + [_I] * 4 + [_L, _L, _F, _P]),

@@ -37,6 +37,7 @@ struct AttnArgs {
   long ldo;        // elements between consecutive tokens of O
   long o_bstride;  // elements between batches of O
   float scale_log2e;
+  int kv_len;      // attn_fwd64_kernel<true, true> only: keys >= kv_len are masked (S is the allocated length Sa there)
 };
 
 // K tile image: [64 keys][16 chunks of 16 B], chunk ^= key & 15
@@ -342,19 +343,27 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
 // from a block's second tile on the MFMA accumulator of a score tile starts at -m, so the softmax is v_exp_f32 straight from the
 // accumulator (no multiply-add per score: the loop is VALU-issue-bound, gen/attn_fwd64.py).
 #include "attn_fwd64_body.inc"
+// KV (attn_fwd64qk_body.inc, mgx_attn_fwd_log2_kv): the ACC stream with a masked key tail.  Everything is allocated at S = Sa,
+// keys >= kv_len (Sa - 256 < kv_len <= Sa) get probability exactly 0: trailing tiles without a valid key are dropped in pairs,
+// and the last two tiles that remain -- peeled out of the loop, whose body is the ACC stream's -- overwrite the scores of
+// masked keys with -inf before their softmax; a padding query row reads Q row kv_len - 1 (gen/attn_fwd64.py, "Masked key tail").
 #include "attn_fwd64q_body.inc"
+#include "attn_fwd64qk_body.inc"
 
 #define ATTN_FWD64_OPERANDS \
   [tid] "v"(threadIdx.x), [q_lo] "s"((unsigned)qp), [q_hi] "s"((unsigned)(qp >> 32)), [k_lo] "s"((unsigned)kp), \
                  [k_hi] "s"((unsigned)(kp >> 32)), [v_lo] "s"((unsigned)vp), [v_hi] "s"((unsigned)(vp >> 32)), \
                  [o_lo] "s"((unsigned)op), [o_hi] "s"((unsigned)(op >> 32)), [l_lo] "s"((unsigned)lp), \
                  [l_hi] "s"((unsigned)(lp >> 32)), [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)), [cs] "s"(g.scale_log2e), \
-                 [nloop] "s"((ntiles - 2) >> 1), [kmax] "s"((ntiles - 1) * 16384), [vmax] "s"((ntiles - 1) * 128), \
+                 [nloop] "s"(nloop), [kmax] "s"((ntiles - 1) * 16384), [vmax] "s"((ntiles - 1) * 128), \
                  [nblk] "s"(count), [qt0] "s"(qt), [hh0] "s"(hh), [b0] "s"(b), [nq] "s"(nq), [nh] "s"(g.H), [kstep] "s"(g.S * 256), \
                  [ostep] "s"(ostep), [obs] "s"((int)(g.o_bstride * 2)), [ob_lo] "s"((unsigned)ob), [ob_hi] "s"((unsigned)(ob >> 32)), \
                  [sq] "s"(stride % nq), [dbh] "s"(stride / nq), [qstride] "s"(stride * 65536), [lstride] "s"(stride * 1024)
+// KV: four bytes, 8 + the number of valid keys (0 .. 64) of the first tile and of the last three (gen/attn_fwd64.py, mask_key)
+#define ATTN_FWD64_KV_OPERANDS \
+  ATTN_FWD64_OPERANDS, [kt] "s"(kt), [kvm1] "s"(g.kv_len - 1)
 
-template <bool ACC>
+template <bool ACC, bool KV = false>
 __global__ void __launch_bounds__(256, 1) attn_fwd64_kernel(AttnArgs g) {
   // Persistent: the blocks (batch, head, q-tile) are cut into 8 contiguous ranges, one per XCD (blockIdx & 7 under round-robin
   // dispatch: speed only); workgroup j of an XCD takes blocks lo + j, lo + j + stride, ...  (stride = workgroups per XCD), so the
@@ -385,9 +394,17 @@ __global__ void __launch_bounds__(256, 1) attn_fwd64_kernel(AttnArgs g) {
   const unsigned long long ob = (unsigned long long)g.O;
   const unsigned long long op = (unsigned long long)(g.O + (long)b * g.o_bstride + (long)(qt * 256) * g.ldo + hh * HD);
   const unsigned long long lp = g.lse ? (unsigned long long)(g.lse + (long)bh * g.S + qt * 256) : 0ull;
-  const int ntiles = g.S >> 6;
+  // K / V^T tiles walked.  KV: those with a valid key, rounded up to a pair (the loop is unrolled by two), at least four
+  // (first tile, one peeled pair, last tile: at S = 256 nothing is dropped and up to all four tiles are partial)
+  const int ntiles = KV ? max(4, (((g.kv_len + 63) >> 6) + 1) & ~1) : g.S >> 6;
+  const int nloop = KV ? (ntiles - 4) >> 1 : (ntiles - 2) >> 1;
   const int ostep = (int)(g.ldo * 512);                       // bytes of 256 rows of O
-  if constexpr (ACC) asm volatile(ATTN_FWD64Q_BODY : : ATTN_FWD64_OPERANDS : ATTN_FWD64Q_CLOBBERS);
+  auto kv_tile = [&](int t) { return 8 + min(64, max(0, g.kv_len - 64 * t)); };
+  // (readfirstlane: the clamp is selected as a vector med3, and an "s" operand has to be in a scalar register)
+  [[maybe_unused]] const int kt = __builtin_amdgcn_readfirstlane(kv_tile(0) | kv_tile(ntiles - 3) << 8 | kv_tile(ntiles - 2) << 16 |
+                                                                 kv_tile(ntiles - 1) << 24);
+  if constexpr (KV) asm volatile(ATTN_FWD64QK_BODY : : ATTN_FWD64_KV_OPERANDS : ATTN_FWD64QK_CLOBBERS);
+  else if constexpr (ACC) asm volatile(ATTN_FWD64Q_BODY : : ATTN_FWD64_OPERANDS : ATTN_FWD64Q_CLOBBERS);
   else asm volatile(ATTN_FWD64_BODY : : ATTN_FWD64_OPERANDS : ATTN_FWD64_CLOBBERS);
 }
 
@@ -420,6 +437,7 @@ static int attn_fwd_any(const uint16_t* Q, const uint16_t* K, const uint16_t* Vt
   g.Q = Q; g.K = K; g.Vt = Vt; g.O = O; g.lse = lse;
   g.B = B; g.H = H; g.S = S; g.Sp = Sp; g.ldo = ldo; g.o_bstride = o_bstride;
   g.scale_log2e = scale_log2e;
+  g.kv_len = S;
   static const int nw = getenv("MGX_ATTN_NW") ? atoi(getenv("MGX_ATTN_NW")) : 8;
   static const int defer = getenv("MGX_ATTN_DEFER") ? atoi(getenv("MGX_ATTN_DEFER")) : 1;
   const int lds = 2 * (K_TILE_BYTES + V_TILE_BYTES);
@@ -455,6 +473,38 @@ extern "C" int mgx_attn_fwd(const uint16_t* Q, const uint16_t* K, const uint16_t
 extern "C" int mgx_attn_fwd_log2(const uint16_t* Q2, const uint16_t* K, const uint16_t* Vt, uint16_t* O, float* lse, int B,
                                  int H, int S, int Sp, long ldo, long o_bstride, void* stream) {
   return attn_fwd_any(Q2, K, Vt, O, lse, B, H, S, Sp, ldo, o_bstride, 1.0f, true, stream);
+}
+
+// The 64-wide forward with a masked key tail takes a problem when the plain one takes it at S = Sp = Sa and kv_len lies in the
+// last 256 keys.  The ONE predicate of mgx_attn_fwd_log2_kv and of the mgx_attn_fwd_kv_path query.
+static bool attn_fwd_kv_wide(int B, int H, int Sa, int kv_len, long ldo, long o_bstride, int* grid64_out) {
+  return B > 0 && H > 0 && Sa > 0 && kv_len > Sa - 256 && kv_len <= Sa && o_bstride >= (long)Sa * ldo &&
+         attn_fwd_wide(B, H, Sa, Sa, ldo, o_bstride, grid64_out);
+}
+
+extern "C" int mgx_attn_fwd_log2_kv(const uint16_t* Q2, const uint16_t* K, const uint16_t* Vt, uint16_t* O, float* lse, int B,
+                                    int H, int Sa, int kv_len, long ldo, long o_bstride, void* stream) {
+  MGX_REQUIRE(Q2 && K && Vt && O, "null operand");
+  MGX_REQUIRE(ldo % 4 == 0 && o_bstride % 4 == 0, "output strides must keep 8-byte alignment");
+  int grid64 = 0;
+  if (!attn_fwd_kv_wide(B, H, Sa, kv_len, ldo, o_bstride, &grid64)) return 1;   // nothing launched: the caller's unpadded path
+  AttnArgs g;
+  g.Q = Q2; g.K = K; g.Vt = Vt; g.O = O; g.lse = lse;
+  g.B = B; g.H = H; g.S = Sa; g.Sp = Sa; g.ldo = ldo; g.o_bstride = o_bstride;
+  g.scale_log2e = 1.0f;
+  g.kv_len = kv_len;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)attn_fwd64_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    attr = true;
+  }
+  attn_fwd64_kernel<true, true><<<grid64, 256, 65536, (hipStream_t)stream>>>(g);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int mgx_attn_fwd_kv_path(int B, int H, int Sa, int kv_len, long ldo, long o_bstride) {
+  return attn_fwd_kv_wide(B, H, Sa, kv_len, ldo, o_bstride, nullptr) ? 1 : 0;
 }
 
 extern "C" int mgx_attn_fwd_path(int B, int H, int S, int Sp, long ldo, long o_bstride) {

@@ -40,13 +40,31 @@ softmax's `v_fma_f32 t, s, c, -mc` -- one of the ~3.5 single-issue instructions 
 at 2552 cycles per iteration against the pipe's 2048 -- disappears: v_exp_f32 reads the accumulator directly.  The first tile
 (scores needed before m exists) still subtracts, with v_sub_f32.
 
+Masked key tail (`kv_tail`, attn_fwd64qk_body.inc, entry point mgx_attn_fwd_log2_kv): the ACC stream for a sequence that was
+padded to a multiple of 256 (720 x 720: 512 + 2025 = 2537 tokens -> Sa = 2560), so that this kernel applies at all.  Everything
+is allocated at Sa; keys >= kv_len (Sa - 256 < kv_len <= Sa) must get probability exactly 0 whatever finite values the padding
+holds.  The loop pays nothing -- its text is the ACC stream's line for line:
+  * trailing tiles without a valid key are dropped in pairs (the launcher shortens the walk: nloop, kmax, vmax; `kv_operands`),
+    so the masked keys lie in the last two tiles that remain;
+  * the loop runs one trip less and its last pair is emitted once more behind it.  In the last two iterations (the second of
+    that pair and LAST) every score is overwritten with -inf unless its key is valid, before the chain's softmax reads it:
+    one v_cmp + one v_cndmask per score, in the MFMA-gap slot the ACC stream's multiply-add left free (`mask_key`; S register
+    e of a chain is key 16 (e >> 3) + 8 h + (e & 7), so the threshold is per lane half).  exp2(-inf) = 0: P, the row sums and
+    O see nothing of the key, and the fix-up, which reads the same registers, stays right;
+  * only at Sa = 256 can the first tile (kv_len < 64) or the third from the end (kv_len < 128) be partial: they carry the same
+    masks as a block in front of the softmax, branched around by one s_cmp (`mask_block`);
+  * a padding QUERY row reads row kv_len - 1 of Q instead of its own (`q_offsets`, two VALU per chain and block): what the
+    padding rows of Q hold can then neither overflow nor, through a fix-up taken by the whole chain, move a bit of a valid row.
+    All Sa rows of O / lse are still computed and stored.
+kv_len = Sa masks nothing and gives the ACC stream's bits.  No scalar memory writes, like every stream here.
+
 This file holds what is this kernel's own; the emitters it shares with the two backward generators (which are built the
 same way: read this docstring first) are in csrc/gen/emit.py: line buffer, counted loop, lane decode, the K / V^T tile
 images' addresses, the LDS-DMA idiom and `segment`, the store block, the .inc text.  Which stream is generated is an argument
 (`Variant`), never module state.
 
-Run `python mixgrpo_amd/csrc/gen/attn_fwd64.py` to rewrite mixgrpo_amd/csrc/attn_fwd64_body.inc and attn_fwd64q_body.inc
-(build.py does); `--diag [--acc] [--timing-only=nodma,nolds,novalu,nobarrier]` writes scratch/attn_fwd64_diag_body.inc.
+Run `python mixgrpo_amd/csrc/gen/attn_fwd64.py` to rewrite mixgrpo_amd/csrc/attn_fwd64_body.inc, attn_fwd64q_body.inc and
+attn_fwd64qk_body.inc (build.py does); `--print [--acc | --kv-tail]` writes a bare stream to stdout; `--diag [--acc] [--timing-only=nodma,nolds,novalu,nobarrier]` writes scratch/attn_fwd64_diag_body.inc.
 """
 import os
 import sys
@@ -64,6 +82,7 @@ class Variant:
     acc: bool = False
     diag: bool = False
     timing_only: frozenset = frozenset()
+    kv_tail: bool = False     # attn_fwd64qk (ACC only): keys >= kv_len are masked, "Masked key tail" in the module docstring
 
 
 # ------------------------------------------------------------------------------------------------ register map
@@ -90,6 +109,9 @@ V_LAST = 239
 NM_A, NM_B = 240, X + 16  # ACC variant: v[240:255] / v[216:231] = 16 x (-m) of chain A / B, the SrcC of a score tile's first MFMA
                           # (X + 16 .. X + 31 is otherwise only the epilogue's staging: dead while the blocks are live)
 DBG_OFF, DBG_LO = 237, 238   # v237, v[238:239]: diagnostic builds only
+KTMP, NINF, H8, KT_2, KT_3 = X + 3, X + 4, X + 5, X + 6, X + 7   # kv_tail: v[203:207] (nothing else behind the prologue uses them)
+                          # = a temporary, -inf, 8 * lane half, the lane thresholds of the last two tiles
+QROW, QH16 = 237, 238     # kv_tail (never diagnostic): the lane's query row w * 64 + r of chain A, 16 * lane half
 
 # scalars (copied from the asm operands into fixed registers, all clobbered)
 sW, sWOFF = 64, 65
@@ -101,6 +123,7 @@ sQ, sK, sV, sO, sL = 74, 76, 78, 80, 82
 sSP2, sLDO2, sCS, sNLOOP, sKMAX, sVMAX = 84, 85, 86, 87, 88, 89
 sRET = 90                 # pair: diagnostic stamps; the K(1) prefetch pointer of the next block
 sDBG = 92                 # pair (diagnostic builds)
+sKT0, sKT1, sKTX = 92, 93, 99    # kv_tail builds (never diagnostic): the mask blocks' tile counts, a prologue temporary
 sLEFT, sQT, sHH, sADV, sWRAP = 94, 95, 96, 97, 98       # block loop: blocks left, (q-tile, head) of the block, flags
 sQTN, sBB = 84, 85               # next q-tile, batch (sSP2 / sLDO2's registers: those are read by the address set-up only)
 S_FIRST, S_LAST = 64, 99
@@ -212,7 +235,45 @@ def block_advance_stores(A):
     A.e(f"s_sub_u32 {s(sLEFT)}, {s(sLEFT)}, 1")
 
 
-def softmax_gaps(var, ch, ngaps=32, first_tile=False):
+def mask_key(ch, e, thr):
+    """kv_tail: S register e of a chain is key 16 (e >> 3) + 8 h + (e & 7) of the tile (h = lane half); `thr` (a VGPR) holds
+    8 + (valid keys of the tile, 0 .. 64) - 8 h, so the key is masked -- its score becomes -inf, its P exactly 0 -- unless
+    8 + 16 (e >> 3) + (e & 7) < thr.  Unsigned on both sides by construction (the 8)."""
+    return [f"v_cmp_lt_u32 vcc, {8 + 16 * (e >> 3) + (e & 7)}, {thr}",
+            f"v_cndmask_b32 {v(ch.S + e)}, {v(NINF)}, {v(ch.S + e)}, vcc"]     # (vcc is the one constant-bus operand)
+
+
+def mask_block(A, ch, kt, tag):
+    """kv_tail: a whole tile's masks in front of its softmax, branched around unless the tile has a masked key (valid keys
+    %[kt] - 8 < 64).  For the tiles that are partial only when Sa = 256: the block's first tile (before its maximum is taken)
+    and the third tile from the end (kt: the SGPR of its count).  Not scheduled, and its label carries no running number: the loop's labels keep theirs."""
+    skip = f".Lkv{tag}{ch.name}_%="
+    A.e(f"s_cmp_ge_u32 {s(kt)}, 72")
+    A.e(f"s_cbranch_scc1 {skip}")
+    A.e("s_nop 7")
+    A.e("s_nop 7")                                          # every MFMA that wrote S of this chain has retired
+    A.e(f"v_sub_u32 {v(KTMP)}, {s(kt)}, {v(H8)}")
+    for e in range(32):
+        for x in mask_key(ch, e, v(KTMP)):
+            A.e(x)
+    A.label(skip)
+
+
+def q_offsets(qt):
+    """kv_tail: Q fragment offsets of the block at q-tile `qt` (an SGPR or operand).  A query row >= kv_len (the last q-tile
+    only) reads row kv_len - 1 instead of its own: the padding rows of Q are never read, so nothing they hold can reach the
+    valid rows of their chain through the rescale fix-up, and their own O / lse -- copies of row kv_len - 1 -- are finite."""
+    out = [f"s_lshl_b32 {s(sTMP)}, {qt}, 8", f"s_sub_u32 {s(sTMP)}, %[kvm1], {s(sTMP)}"]      # last valid row of the tile (>= 0)
+    for off, add in ((QOFF_A, None), (QOFF_B, 32)):
+        row = v(QROW)
+        if add:
+            out.append(f"v_add_u32 {v(KTMP)}, {add}, {v(QROW)}")
+            row = v(KTMP)
+        out += [f"v_min_u32 {v(KTMP)}, {s(sTMP)}, {row}", f"v_lshl_add_u32 {v(off)}, {v(KTMP)}, 8, {v(QH16)}"]
+    return out
+
+
+def softmax_gaps(var, ch, ngaps=32, first_tile=False, thr=None):
     """VALU stream of one chain's tile softmax, as `ngaps` lists (one per MFMA gap) + a tail list.
 
     Element e (0..31) = S register e; fma(e) two gaps before exp(e), the sum one gap after, cvt_pk(k) one gap after the
@@ -225,6 +286,9 @@ def softmax_gaps(var, ch, ngaps=32, first_tile=False):
         if var.acc:
             return f"v_sub_f32 {t(e)}, {v(ch.S + e)}, {v(ch.MC)}" if first_tile else None
         return f"v_fma_f32 {t(e)}, {v(ch.S + e)}, {s(sCS)}, -{v(ch.MC)}"
+
+    def mask(e):                            # kv_tail, a peeled tile: in the slot the ACC stream's fma left free
+        return mask_key(ch, e, thr) if thr is not None else []
 
     def exp(e):
         if var.acc and not first_tile:
@@ -242,10 +306,12 @@ def softmax_gaps(var, ch, ngaps=32, first_tile=False):
         return f"v_cvt_pk_bf16_f32 {v(ch.P + k)}, {t(2 * k)}, {t(2 * k + 1)}"
 
     gaps = [[] for _ in range(32)]
-    gaps[0] += [x for x in (fma(0), fma(1), fma(2), fma(3)) if x] + [exp(0), exp(1)]
+    gaps[0] += [x for e in range(4) for x in mask(e)] + [x for x in (fma(0), fma(1), fma(2), fma(3)) if x] + [exp(0), exp(1)]
     for g in range(1, 32):
         if g + 1 < 32:
             gaps[g].append(exp(g + 1))
+        if g + 3 < 32:
+            gaps[g] += mask(g + 3)
         if g + 3 < 32 and fma(g + 3):
             gaps[g].append(fma(g + 3))
         if g == 1:
@@ -338,13 +404,18 @@ def fixup(A, var, ch, back):
     A.e(f"s_branch {back}")
 
 
-def iteration(A, var, par, fixups, first=False, last=False):
-    """One K/V tile i with i & 1 == par.  Slots: K(j), V(j) live in slot j & 1."""
-    A.c(f"================ iteration parity {par}{' FIRST' if first else ''}{' LAST' if last else ''}")
+def iteration(A, var, par, fixups, first=False, last=False, thr=None, kt=None):
+    """One K/V tile i with i & 1 == par.  Slots: K(j), V(j) live in slot j & 1.
+    kv_tail, peeled iterations only: thr = the VGPR of the tile's lane threshold (masks in the softmax's gaps), or kt = the
+    SGPR of the tile's valid-key count + 8 (a branched-around `mask_block` in front of each chain's softmax)."""
+    A.c(f"================ iteration parity {par}{' FIRST' if first else ''}{' LAST' if last else ''}"
+        f"{' MASKED' if thr or kt else ''}")
+    if kt:
+        mask_block(A, CA, kt, "f" if first else "p")
     # ---------------- segment 1: MFMA chain B (P V of tile i-1, S^T of tile i), softmax chain A
     mf = ([] if first else [mfma_pv(CB, n) for n in range(16)]) + [mfma_qk(var, CB, n, first_tile=first) for n in range(16)]
     ng = len(mf)
-    vg, vt = softmax_gaps(var, CA, ng, first_tile=first)
+    vg, vt = softmax_gaps(var, CA, ng, first_tile=first, thr=thr)
     pre = []
     if first:
         pre = max_prefix(var, CA)
@@ -353,7 +424,7 @@ def iteration(A, var, par, fixups, first=False, last=False):
         # the NEXT block's first tiles and Q fragments (the same block again when this is the workgroup's last: unused):
         # K(0), V^T(0) -> slot 0 and K(1) -> slot 1 are free since the barrier behind iteration nt-2; Q_A since then too, Q_B
         # after its last S^T product in this segment
-        pre = block_advance_loads() + pre
+        pre = block_advance_loads() + (q_offsets(s(sQTN)) if var.kv_tail else []) + pre
         pieces = ([dma_piece("k", p, 0) for p in range(4)] + [dma_piece("v", p, 0) for p in range(4)] +
                   [dma_piece("k", p, 1, ptr=sRET) for p in range(4)])
         for j, pc in enumerate(pieces):
@@ -375,7 +446,9 @@ def iteration(A, var, par, fixups, first=False, last=False):
     end_of_softmax(A, CA, fixups, first)
     # ---------------- segment 2: MFMA chain A (P V of tile i, S^T of tile i+1), softmax chain B
     mf = [mfma_pv(CA, n) for n in range(16)] + ([] if last else [mfma_qk(var, CA, n) for n in range(16)])
-    vg, vt = softmax_gaps(var, CB, 32 if not last else 16, first_tile=first)
+    if kt:
+        mask_block(A, CB, kt, "f" if first else "p")
+    vg, vt = softmax_gaps(var, CB, 32 if not last else 16, first_tile=first, thr=thr)
     pre = max_prefix(var, CB) if first else []
     lds, waits = {}, {0: "s_waitcnt lgkmcnt(0)"}            # every V^T fragment of the tile has landed
     if not last:
@@ -405,7 +478,7 @@ def end_of_softmax(A, ch, fixups, first):
 
 
 # ------------------------------------------------------------------------------------------------ prologue / epilogue
-def prologue(A):
+def prologue(A, var):
     A.c("inputs -> fixed scalar registers")
     for dst, name in ((sQ, "q_lo"), (sQ + 1, "q_hi"), (sK, "k_lo"), (sK + 1, "k_hi"), (sV, "v_lo"), (sV + 1, "v_hi"),
                       (sO, "o_lo"), (sO + 1, "o_hi"), (sL, "l_lo"), (sL + 1, "l_hi"), (sSP2, "sp2"), (sLDO2, "ldo2"),
@@ -435,6 +508,24 @@ def prologue(A):
     A.e(f"s_lshl_b32 {s(sTMP)}, {s(sLDO2)}, 5")
     A.e(f"v_add_u32 {v(OOFF_B)}, {s(sTMP)}, {v(OOFF_A)}")
     A.e(f"v_lshlrev_b32 {v(LOFF)}, 2, {t0}")
+    if var.kv_tail:
+        A.c("Q offsets with the padding rows redirected (q_offsets)")
+        A.e(f"v_mov_b32 {v(QROW)}, {t0}")
+        A.e(f"v_lshlrev_b32 {v(QH16)}, 4, {h}")
+        A.e(f"v_lshlrev_b32 {v(H8)}, 3, {h}")                              # (the lane decode's registers end here)
+        for x in q_offsets("%[qt0]"):
+            A.e(x)
+        A.c("masked key tail: %[kt] = four bytes, 8 + the valid keys (0 .. 64) of the first tile and of the last three;")
+        A.c("lane thresholds of the last two tiles (mask_key)")
+        A.e(f"v_mov_b32 {v(NINF)}, 0xff800000")
+        A.e(f"s_and_b32 {s(sKT0)}, %[kt], 0xff")
+        A.e(f"s_lshr_b32 {s(sKT1)}, %[kt], 8")
+        A.e(f"s_and_b32 {s(sKT1)}, {s(sKT1)}, 0xff")
+        A.e(f"s_lshr_b32 {s(sKTX)}, %[kt], 16")
+        A.e(f"s_and_b32 {s(sKTX)}, {s(sKTX)}, 0xff")
+        A.e(f"v_sub_u32 {v(KT_2)}, {s(sKTX)}, {v(H8)}")
+        A.e(f"s_lshr_b32 {s(sKTX)}, %[kt], 24")
+        A.e(f"v_sub_u32 {v(KT_3)}, {s(sKTX)}, {v(H8)}")
     A.c("block loop state; the first block's tiles K(0), V^T(0) -> slot 0, K(1) -> slot 1 and its Q fragments")
     A.e(f"s_mov_b32 {s(sLEFT)}, %[nblk]")
     A.e(f"s_mov_b32 {s(sQT)}, %[qt0]")
@@ -522,8 +613,9 @@ def stamp(A, k, clock="s_memtime"):
     A.e("s_mov_b64 exec, -1")
 
 
-def generate(diag=False, acc=False, timing_only=()):
-    var = Variant(acc=acc, diag=diag, timing_only=frozenset(timing_only))
+def generate(diag=False, acc=False, timing_only=(), kv_tail=False):
+    var = Variant(acc=acc, diag=diag, timing_only=frozenset(timing_only), kv_tail=kv_tail)
+    assert not kv_tail or (acc and not diag), "the masked key tail exists for the ACC stream only (s92, s93 are the stamps')"
     A = Asm()
     fixups = []
     if var.diag:
@@ -532,19 +624,22 @@ def generate(diag=False, acc=False, timing_only=()):
         A.e(f"v_lshrrev_b32 {v(DBG_OFF)}, 6, %[tid]")
         A.e(f"v_lshlrev_b32 {v(DBG_OFF)}, 6, {v(DBG_OFF)}")         # 64 bytes of stamps per wave
         stamp(A, 0)
-    prologue(A)
+    prologue(A, var)
     block = A.new_label("block")
     A.label(block)
     block_start(A, var)
     if var.diag:
         stamp(A, 1)
-    iteration(A, var, 0, fixups, first=True)
+    iteration(A, var, 0, fixups, first=True, kt=sKT0 if var.kv_tail else None)
     if var.diag:
         stamp(A, 2)
     emit.counted_loop(A, sLOOP, sNLOOP, lambda: iteration(A, var, 1, fixups), lambda: iteration(A, var, 0, fixups))
     if var.diag:
         stamp(A, 3)
-    iteration(A, var, 1, fixups, last=True)
+    if var.kv_tail:                                                     # the loop runs one trip less: its last pair is peeled
+        iteration(A, var, 1, fixups, kt=sKT1)
+        iteration(A, var, 0, fixups, thr=v(KT_2))
+    iteration(A, var, 1, fixups, last=True, thr=v(KT_3) if var.kv_tail else None)
     if var.diag:
         stamp(A, 4)
     epilogue(A)
@@ -566,23 +661,36 @@ def generate(diag=False, acc=False, timing_only=()):
     return A.text()
 
 
+def kv_operands(kv_len):
+    """kv_tail: what the launcher derives from kv_len (csrc/attention.hip restates it; the CPU tests feed the interpreter from
+    here): the tiles walked -- those with a valid key, rounded up to a pair, at least four --, the loop's trips (its last pair
+    is peeled), the clamps of the tile fetch, kt = four bytes, lowest first: 8 + the valid keys (0 .. 64) of the first tile
+    and of the last three, and the last valid row."""
+    nt = max(4, ((kv_len + 63) // 64 + 1) & ~1)
+    kt = lambda i: 8 + min(64, max(0, kv_len - 64 * i))
+    return dict(nloop=(nt - 4) // 2, kmax=(nt - 1) * SLOT, vmax=(nt - 1) * 128,
+                kt=kt(0) | kt(nt - 3) << 8 | kt(nt - 2) << 16 | kt(nt - 1) << 24, kvm1=kv_len - 1)
+
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_BODY = os.path.join(HERE, "..", "attn_fwd64_body.inc")
 OUT_BODY_Q = os.path.join(HERE, "..", "attn_fwd64q_body.inc")
+OUT_BODY_QK = os.path.join(HERE, "..", "attn_fwd64qk_body.inc")
 
 
-def render(diag=False, acc=False, timing_only=()):
+def render(diag=False, acc=False, timing_only=(), kv_tail=False):
     # ACC: v[240:255] hold chain A's -m block
-    return emit.render("ATTN_FWD64Q" if acc else "ATTN_FWD64", __file__, generate(diag, acc, timing_only),
-                       emit.clobbers(255 if acc else V_LAST, S_FIRST, S_LAST))
+    return emit.render("ATTN_FWD64QK" if kv_tail else "ATTN_FWD64Q" if acc else "ATTN_FWD64", __file__,
+                       generate(diag, acc, timing_only, kv_tail), emit.clobbers(255 if acc else V_LAST, S_FIRST, S_LAST))
 
 
 def write():
-    return tuple(emit.write_if_changed(path, render(acc=acc)) for path, acc in ((OUT_BODY, False), (OUT_BODY_Q, True)))
+    return tuple(emit.write_if_changed(path, render(acc=acc, kv_tail=kv)) for path, acc, kv in
+                 ((OUT_BODY, False, False), (OUT_BODY_Q, True, False), (OUT_BODY_QK, True, True)))
 
 
 if __name__ == "__main__":
-    acc = "--acc" in sys.argv
+    acc = "--acc" in sys.argv or "--kv-tail" in sys.argv
     timing = [x for a_ in sys.argv if a_.startswith("--timing-only=") for x in a_.split("=")[1].split(",")]
     if "--diag" in sys.argv and "--print" not in sys.argv:      # scratch/fwd64_diag.hip includes this one
         out = os.path.join(HERE, "..", "..", "..", "scratch", "attn_fwd64_diag_body.inc")
@@ -590,4 +698,4 @@ if __name__ == "__main__":
             f.write(render(diag=True, acc=acc, timing_only=timing))
         print(out)
     else:
-        emit.main(lambda: generate("--diag" in sys.argv, acc, timing), write)
+        emit.main(lambda: generate("--diag" in sys.argv, acc, timing, "--kv-tail" in sys.argv), write)

@@ -199,6 +199,8 @@ class _Work:
     slices of it (`view`), so the rollout (B = G), the shared first step (B = 1) and the replay micro-batches share one
     allocation instead of one per batch size."""
 
+    kv_len = None     # set by the padded no-grad forward for the length of one call: the keys >= kv_len of S are padding
+
     def __init__(self, cfg, B, L, N, device):
         d, H, hd = cfg.dim, cfg.num_attention_heads, cfg.attention_head_dim
         S = L + N
@@ -236,6 +238,8 @@ class _Work:
 
 class _WorkView:
     """The first B batches of a `_Work` (all buffers are batch-major and contiguous, so these are plain prefixes)."""
+
+    kv_len = None
 
     def __init__(self, base, B):
         assert B <= base.B
@@ -277,6 +281,8 @@ class FluxTransformer2DModel(torch.nn.Module):
         self._work: Dict[Tuple[int, int], _Work] = {}
         self._rope_cache = {}
         self.recompute = True
+        self.last_route = None                    # of the last no-grad forward: "plain" | "padded_kv" (ops.ATTN_PAD_KV)
+        self.padded_kv_calls = 0
 
     # ------------------------------------------------------------------ parameters / checkpoints
     def state_dict(self, *args, **kwargs):
@@ -363,6 +369,10 @@ class FluxTransformer2DModel(torch.nn.Module):
             q8, k8, v8t, amax = w.fp8_operands()
             ops.attn_fp8_quantize(w.Q, w.K, w.Vt, q8, k8, v8t, amax, w.B, H, w.S, w.Sp)
             ops.attn_fwd_fp8(q8, k8, v8t, amax, O, lse, w.B, H, w.S, w.Sp, ldo, o_bstride, scale)
+        elif ops.Q_PRESCALE and w.kv_len is not None:
+            # padded no-grad forward: every buffer is allocated at w.S (% 256 == 0), the image rows >= kv_len are padding
+            if not ops.attn_fwd_log2_kv(w.Q, w.K, w.Vt, O, lse, w.B, H, w.S, w.kv_len, ldo, o_bstride):
+                raise MgxError(f"mgx_attn_fwd_log2_kv refused B {w.B} H {H} Sa {w.S} kv_len {w.kv_len} after its path query took it")
         elif ops.Q_PRESCALE:
             ops.attn_fwd_log2(w.Q, w.K, w.Vt, O, lse, w.B, H, w.S, w.Sp, ldo, o_bstride)
         else:
@@ -641,11 +651,58 @@ class FluxTransformer2DModel(torch.nn.Module):
                                        pooled_projections, img_ids)
         return (out,)
 
+    def _pad_kv_rows(self, B, L, N):
+        """Image rows of the padded no-grad forward (ops.ATTN_PAD_KV), or None for the plain one: a sequence off 256 is run
+        at the next multiple of 256 with the added keys masked (`mgx_attn_fwd_log2_kv`), so that the 64-query attention
+        forward and the fused q | k / V^T projections take it (720 x 720: 512 + 2025 = 2537 -> 2560, image rows 2048).
+        Forward only: the training forward / backward / replay have no masked backward and keep the unpadded kernels."""
+        S = L + N
+        if not ops.ATTN_PAD_KV or S % 256 == 0 or not ops.Q_PRESCALE or self.attention_dtype != "bf16":
+            return None
+        d, H = self.cfg.dim, self.cfg.num_attention_heads
+        Sa = (S + 255) // 256 * 256
+        # (ldo, batch stride) of the double blocks' O and of the single blocks' [O | mlp] operand
+        if not all(ops.attn_fwd_kv_path(B, H, Sa, S, ld, Sa * ld) == 1 for ld in (d, 5 * d)):
+            return None
+        return Sa - L
+
+    def _padded_inputs(self, hidden_states, img_ids, N_pad):
+        """hidden_states [B, N, C] / img_ids [N, 3] with zero rows appended up to N_pad.  The padded ids are cached with the
+        tensor they were made from, so that the RoPE tables (cached on their ids' identity) are not rebuilt every call."""
+        B, N, C = hidden_states.shape
+        hs = hidden_states.new_zeros(B, N_pad, C)
+        hs[:, :N] = hidden_states
+        key = (id(img_ids), img_ids._version, tuple(img_ids.shape), N_pad)
+        hit = self._rope_cache.get("pad_ids")
+        if hit is None or hit[0] != key:
+            ids = torch.cat([img_ids, img_ids.new_zeros(N_pad - N, img_ids.shape[1])], dim=0)
+            hit = (key, ids, img_ids)
+            self._rope_cache["pad_ids"] = hit
+        return hs, hit[1]
+
     def _forward_nograd(self, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections,
                         img_ids, collect=None):
         B, N, _ = hidden_states.shape
         L = encoder_hidden_states.shape[1]
-        w = self._workspace(B, L, N)
+        N_pad = self._pad_kv_rows(B, L, N) if collect is None else None
+        if N_pad is not None:
+            hs, ids = self._padded_inputs(hidden_states, img_ids, N_pad)
+            w = self._workspace(B, L, N_pad)
+            w.kv_len = L + N
+            try:
+                out = self._forward_nograd_on(w, hs, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections, ids, None)
+            finally:
+                w.kv_len = None
+            self.last_route = "padded_kv"
+            self.padded_kv_calls += 1
+            return out[:, :N].contiguous()
+        self.last_route = "plain"
+        return self._forward_nograd_on(self._workspace(B, L, N), hidden_states, encoder_hidden_states, timestep, guidance, txt_ids,
+                                       pooled_projections, img_ids, collect)
+
+    def _forward_nograd_on(self, w, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections,
+                           img_ids, collect):
+        B, L = w.B, w.L
         self._embed(w, hidden_states, encoder_hidden_states)
         temb, st = self._temb(B, timestep.to(self.store.device), guidance, pooled_projections)
         cos, sin = self._rope(txt_ids, img_ids)

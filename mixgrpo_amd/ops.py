@@ -235,6 +235,28 @@ def attn_fwd_path(B, H, S, Sp, ldo, o_bstride):
     return r
 
 
+# The no-grad forward pads a sequence that is off 256 to the next multiple and masks the padded keys (attn_fwd_log2_kv), so that
+# the 64-query attention and the fused projections apply (flux.py, _forward_nograd).  Off by default: the training replay
+# keeps the unpadded kernels (the backward has no masked tail), so rollout and replay would differ in their attention kernels.
+ATTN_PAD_KV = os.environ.get("MGX_ATTN_PAD_KV", "0") != "0"
+
+
+def attn_fwd_log2_kv(Q2, K, Vt, O_ptr_tensor, lse, B, H, Sa, kv_len, ldo, o_bstride):
+    """attn_fwd_log2 on operands allocated at Sa (% 256 == 0) with the keys >= kv_len masked (`mgx_attn_fwd_log2_kv`).  False --
+    nothing launched -- when the 64-query kernel cannot take the problem (attn_fwd_kv_path): the caller keeps the unpadded path."""
+    rc = lib().mgx_attn_fwd_log2_kv(ptr(Q2), ptr(K), ptr(Vt), O_ptr_tensor.data_ptr(), ptr(lse), B, H, Sa, kv_len, ldo, o_bstride,
+                                    stream())
+    if rc == 1:
+        return False
+    check(rc)
+    return True
+
+
+def attn_fwd_kv_path(B, H, Sa, kv_len, ldo, o_bstride):
+    """1 when attn_fwd_log2_kv takes this problem, 0 when it refuses it.  Launches nothing."""
+    return lib().mgx_attn_fwd_kv_path(B, H, Sa, kv_len, ldo, o_bstride)
+
+
 def attn_bwd_path(B, H, S, Sp, ldo, o_bstride):
     """The kernels attn_bwd launches for this problem: 0 = 8-wave dkv / dq, 1 = the generated 64-wide pair."""
     r = lib().mgx_attn_bwd_path(B, H, S, Sp, ldo, o_bstride)
