@@ -278,7 +278,7 @@ int mgx_attn_bwd_path(int B, int H, int S, int Sp, long ldo, long o_bstride);
  * padding rows of Q2 are not read at all.  Queries are not masked: rows < kv_len of O and lse are softmax attention over the
  * keys 0 .. kv_len - 1 only (lse the natural logarithm over those keys) and do not depend on the padding by a bit; rows
  * >= kv_len are written with unspecified finite values (today: those of row kv_len - 1).  kv_len == Sa gives the bits of
- * mgx_attn_fwd_log2.  Forward only: the backward has no masked tail yet.
+ * mgx_attn_fwd_log2.  Its backward is mgx_attn_bwd_kv.
  * Returns 1 and launches NOTHING when the 64-query kernel cannot take the problem -- mgx_attn_fwd_path(B, H, Sa, Sa, ..) is 0
  * (the persistent walk, Sa % 256, the offset fields, MGX_ATTN_W64=0) or kv_len is out of range: the caller keeps its unpadded
  * path, as with mgx_linear_qk_norm_rope.  mgx_attn_fwd_kv_path is that predicate (1 = taken, 0 = refused), launches nothing. */
@@ -308,6 +308,28 @@ int mgx_attn_bwd(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const 
                  const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt, uint16_t* dQ,
                  uint16_t* dK, uint16_t* dV, int B, int H, int S, int Sp, long ldo, long o_bstride, float scale,
                  void* stream);
+
+/* mgx_attn_bwd with a masked tail: the backward of mgx_attn_fwd_log2_kv (autograd of F.scaled_dot_product_attention,
+ * fastvideo/train_grpo_flux.py:134-144, at a token count off 256), on the generated 64-wide pair and nothing else.
+ * Everything is allocated at Sa, Sa % 256 == 0: Q, K, V, dQ, dK, dV [B,H,Sa,128], Qt, Kt, dOt [B,H,128,Sa], lse, delta
+ * [B,H,Sa], O and dO with Sa rows per batch (o_bstride >= Sa * ldo).  Sa - 256 < kv_len <= Sa; keys AND queries >= kv_len are
+ * padding.  Rows >= kv_len of Q, K, V, O, dO, lse and columns >= kv_len of Qt, Kt may hold ANY FINITE values -- no bound on
+ * their magnitude: what they make of a score or a dP is replaced by a select, never multiplied away, the padding rows of Q, dO,
+ * lse (dQ kernel) and of K, V (dK / dV kernel) are not read at all, and the padding rows of O and dO are not read by the prep.
+ * Rows < kv_len of dQ, dK, dV, and of delta / columns < kv_len of dOt, are the backward of attention over the keys and
+ * queries 0 .. kv_len - 1 only and do not depend on the padding by a bit.  Rows >= kv_len of dQ, dK, dV and of delta, and
+ * columns >= kv_len of dOt, are written as ZERO (dQ / dK / dV possibly -0): the layers behind the attention take nothing from
+ * the padding tokens.  kv_len == Sa gives the bits of mgx_attn_bwd at S = Sp = Sa.  `scale` as mgx_attn_bwd (for the log2
+ * forward: ln 2 on Q2).
+ * Returns 1 and launches NOTHING when the problem cannot be taken -- mgx_attn_bwd_path(B, H, Sa, Sa, ..) is 0 (Sa % 256, the
+ * offset fields, MGX_ATTN_W64=0), kv_len is out of range or o_bstride < Sa * ldo: there is no other kernel behind this entry
+ * point, the caller keeps its unpadded path.  mgx_attn_bwd_kv_path is that predicate (1 = taken, 0 = refused), launches
+ * nothing. */
+int mgx_attn_bwd_kv(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* Qt, const uint16_t* Kt,
+                    const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt, uint16_t* dQ,
+                    uint16_t* dK, uint16_t* dV, int B, int H, int Sa, int kv_len, long ldo, long o_bstride, float scale,
+                    void* stream);
+int mgx_attn_bwd_kv_path(int B, int H, int Sa, int kv_len, long ldo, long o_bstride);
 
 /* out[b, :] = bf16(x[b, :] @ W[N,K]^T + bias), 1 <= Bn <= 16 rows (temb MLPs, AdaLN modulation linears) */
 int mgx_skinny_linear(const uint16_t* x, long ldx, const uint16_t* W, long ldw, const uint16_t* bias, uint16_t* out,

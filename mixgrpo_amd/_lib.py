@@ -80,6 +80,8 @@ SIGNATURES = {
     "mgx_attn_fp8_quantize": (_I, [_P] * 7 + [_I] * 4 + [_P]),
     "mgx_attn_fwd_fp8": (_I, [_P] * 6 + [_I] * 4 + [_L, _L, _F, _P]),
     "mgx_attn_bwd": (_I, [_P] * 13 + [_I] * 4 + [_L, _L, _F, _P]),
+    "mgx_attn_bwd_kv": (_I, [_P] * 13 + [_I] * 4 + [_L, _L, _F, _P]),
+    "mgx_attn_bwd_kv_path": (_I, [_I] * 4 + [_L, _L]),
     "mgx_skinny_linear": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _P]),
     "mgx_skinny_wgrad": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _P]),
     "mgx_skinny_dgrad_workspace": (_L, [_I, _I]),

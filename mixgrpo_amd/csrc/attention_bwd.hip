@@ -98,6 +98,41 @@ __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(const bf16_raw* __re
   }
 }
 
+// The kv_len form (mgx_attn_bwd_kv): everything is allocated at Sa rows / columns, rows >= kv_len are padding.  delta and dOt
+// of the rows < kv_len are the kernel's above bit for bit (the same loads, products and wave_sum); those >= kv_len are
+// written as zero whatever the padding rows of O and dO hold (they are not read).
+__global__ void __launch_bounds__(256) attn_bwd_prep_kv_kernel(const bf16_raw* __restrict__ O, const bf16_raw* __restrict__ dO,
+                                                               long ldo, long o_bstride, float* __restrict__ delta,
+                                                               bf16_raw* __restrict__ dOt, int H, int Sa, int kv_len) {
+  __shared__ bf16_raw tile[64][130];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int hh = blockIdx.y, b = blockIdx.z, t0 = blockIdx.x * 64;
+  for (int i = 0; i < 16; ++i) {
+    const int tl = w * 16 + i, s = t0 + tl;            // s < Sa: Sa % 64 == 0
+    uint32_t ud = 0;
+    float acc = 0.f;
+    if (s < kv_len) {
+      const long off = (long)b * o_bstride + (long)s * ldo + hh * HD + 2 * lane;
+      ud = *reinterpret_cast<const uint32_t*>(dO + off);
+      const uint32_t uo = *reinterpret_cast<const uint32_t*>(O + off);
+      acc = bf2f(ud & 0xffff) * bf2f(uo & 0xffff) + bf2f(ud >> 16) * bf2f(uo >> 16);
+    }
+    *reinterpret_cast<uint32_t*>(&tile[tl][2 * lane]) = ud;
+    acc = wave_sum(acc);
+    if (lane == 0) delta[((long)b * H + hh) * Sa + s] = acc;
+  }
+  __syncthreads();
+  for (int id = threadIdx.x; id < 128 * 8; id += 256) {
+    const int d = id >> 3, c = id & 7;
+    uint4 u;
+    u.x = (uint32_t)tile[c * 8 + 0][d] | ((uint32_t)tile[c * 8 + 1][d] << 16);
+    u.y = (uint32_t)tile[c * 8 + 2][d] | ((uint32_t)tile[c * 8 + 3][d] << 16);
+    u.z = (uint32_t)tile[c * 8 + 4][d] | ((uint32_t)tile[c * 8 + 5][d] << 16);
+    u.w = (uint32_t)tile[c * 8 + 6][d] | ((uint32_t)tile[c * 8 + 7][d] << 16);
+    *reinterpret_cast<uint4*>(dOt + (((long)b * H + hh) * HD + d) * Sa + t0 + c * 8) = u;
+  }
+}
+
 struct BwdArgs {
   const bf16_raw* Q;    // [B,H,S,128]
   const bf16_raw* K;    // [B,H,S,128]
@@ -562,6 +597,97 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_dkv64_kernel(BwdArgs g) {
 #undef HI
 }
 
+// ------------------------------------------------------------------------------------------------ masked tail, 64-wide pair
+// attn_bwd_dq64kv_kernel / attn_bwd_dkv64kv_kernel (mgx_attn_bwd_kv): the two streams above for a sequence padded to
+// g.S = g.Sp = Sa (% 256 == 0); keys and queries >= kv_len (Sa - 256 < kv_len <= Sa) contribute nothing, rows >= kv_len of
+// dQ / dK / dV are stored as zero.  The loops are the unmasked streams' line for line; the masks sit in the iterations outside
+// them ("Masked tail" in gen/attn_bwd_dq64.py and gen/attn_bwd_dkv64.py, whose kv_operands the launch code below restates).
+struct BwdKvArgs {
+  BwdArgs g;
+  int kv_len;
+};
+
+#include "attn_bwd_dq64kv_body.inc"
+
+__global__ void __launch_bounds__(256, 1) attn_bwd_dq64kv_kernel(BwdKvArgs a) {
+  const BwdArgs& g = a.g;
+  const int kv_len = a.kv_len;
+  const int nq = g.S >> 8;
+  int bid = blockIdx.x;
+  xcd_remap(bid, nq * g.H * g.B);
+  const int qt = bid % nq, bh = bid / nq;
+  const int b = bh / g.H, hh = bh - b * g.H;
+  const long bhS = (long)bh * g.S;
+  const unsigned long long qp = (unsigned long long)(g.Q + (bhS + qt * 256) * HD);
+  const unsigned long long kp = (unsigned long long)(g.K + bhS * HD);
+  const unsigned long long vp = (unsigned long long)(g.V + bhS * HD);
+  const unsigned long long ktp = (unsigned long long)(g.Kt + (long)bh * HD * g.Sp);
+  const unsigned long long dop = (unsigned long long)(g.dO + (long)b * g.o_bstride + (long)(qt * 256) * g.ldo + hh * HD);
+  const unsigned long long lsep = (unsigned long long)(g.lse + bhS + qt * 256);
+  const unsigned long long dlp = (unsigned long long)(g.delta + bhS + qt * 256);
+  const unsigned long long dqp = (unsigned long long)(g.dQ + (bhS + qt * 256) * HD);
+  // the 64-key tiles walked: those with a valid key, rounded up to a pair, at least four (the loop's last pair is peeled)
+  const int ntiles = max(4, (((kv_len + 63) >> 6) + 1) & ~1);
+  auto cnt = [&](int j) { return 8 + min(32, max(0, kv_len - 32 * j)); };      // 8 + the valid keys of 32-key block j
+  // (readfirstlane: the clamps are selected as vector med3, and an "s" operand has to be in a scalar register)
+  const int kt0 = __builtin_amdgcn_readfirstlane(cnt(0) | cnt(1) << 8 | cnt(2 * ntiles - 6) << 16 | cnt(2 * ntiles - 5) << 24);
+  const int kt1 = __builtin_amdgcn_readfirstlane(cnt(2 * ntiles - 4) | cnt(2 * ntiles - 3) << 8 | cnt(2 * ntiles - 2) << 16 |
+                                                 cnt(2 * ntiles - 1) << 24);
+  const int qlast = __builtin_amdgcn_readfirstlane(min(255, kv_len - 1 - 256 * qt));   // >= 0: the last block holds a valid row
+  asm volatile(ATTN_BWD_DQ64KV_BODY
+               :
+               : [tid] "v"(threadIdx.x), [q_lo] "s"((unsigned)qp), [q_hi] "s"((unsigned)(qp >> 32)), [k_lo] "s"((unsigned)kp),
+                 [k_hi] "s"((unsigned)(kp >> 32)), [v_lo] "s"((unsigned)vp), [v_hi] "s"((unsigned)(vp >> 32)),
+                 [kt_lo] "s"((unsigned)ktp), [kt_hi] "s"((unsigned)(ktp >> 32)), [do_lo] "s"((unsigned)dop),
+                 [do_hi] "s"((unsigned)(dop >> 32)), [lse_lo] "s"((unsigned)lsep), [lse_hi] "s"((unsigned)(lsep >> 32)),
+                 [dl_lo] "s"((unsigned)dlp), [dl_hi] "s"((unsigned)(dlp >> 32)), [dq_lo] "s"((unsigned)dqp),
+                 [dq_hi] "s"((unsigned)(dqp >> 32)), [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)), [cs] "s"(g.scale_log2e),
+                 [scale] "s"(g.scale), [nloop] "s"((ntiles - 4) >> 1), [seq] "s"(64 * ntiles), [kt0] "s"(kt0), [kt1] "s"(kt1),
+                 [qlast] "s"(qlast)
+               : ATTN_BWD_DQ64KV_CLOBBERS);
+}
+
+#include "attn_bwd_dkv64kv_body.inc"
+
+__global__ void __launch_bounds__(256, 1) attn_bwd_dkv64kv_kernel(BwdKvArgs a) {
+  const BwdArgs& g = a.g;
+  const int kv_len = a.kv_len;
+  const int nkb = g.S >> 8;
+  int bid = blockIdx.x;
+  xcd_remap(bid, nkb * g.H * g.B);
+  const int kt = bid % nkb, bh = bid / nkb;
+  const int b = bh / g.H, hh = bh - b * g.H;
+  const long bhS = (long)bh * g.S;
+  const unsigned long long qp = (unsigned long long)(g.Q + bhS * HD);
+  const unsigned long long dop = (unsigned long long)(g.dO + (long)b * g.o_bstride + hh * HD);
+  const unsigned long long qtp = (unsigned long long)(g.Qt + (long)bh * HD * g.Sp);
+  const unsigned long long dotp = (unsigned long long)(g.dOt + (long)bh * HD * g.Sp);
+  const unsigned long long kp = (unsigned long long)(g.K + (bhS + kt * 256) * HD);
+  const unsigned long long vp = (unsigned long long)(g.V + (bhS + kt * 256) * HD);
+  const unsigned long long lsep = (unsigned long long)(g.lse + bhS);
+  const unsigned long long dlp = (unsigned long long)(g.delta + bhS);
+  const unsigned long long dkp = (unsigned long long)(g.dK + (bhS + kt * 256) * HD);
+  const unsigned long long dvp = (unsigned long long)(g.dV + (bhS + kt * 256) * HD);
+  // the 32-query blocks walked: those with a valid query, rounded up to a pair, at least four (the loop's last pair is peeled)
+  const int nq = max(4, (((kv_len + 31) >> 5) + 1) & ~1);
+  auto cnt = [&](int j) { return 8 + min(32, max(0, kv_len - 32 * j)); };      // 8 + the valid queries of 32-query block j
+  const int qk = __builtin_amdgcn_readfirstlane(cnt(0) | cnt(nq - 3) << 8 | cnt(nq - 2) << 16 | cnt(nq - 1) << 24);
+  const int klast = __builtin_amdgcn_readfirstlane(min(255, kv_len - 1 - 256 * kt));   // >= 0: the last block holds a valid row
+#define LO(x) "s"((unsigned)(x))
+#define HI(x) "s"((unsigned)((x) >> 32))
+  asm volatile(ATTN_BWD_DKV64KV_BODY
+               :
+               : [tid] "v"(threadIdx.x), [q_lo] LO(qp), [q_hi] HI(qp), [do_lo] LO(dop), [do_hi] HI(dop), [qt_lo] LO(qtp),
+                 [qt_hi] HI(qtp), [dot_lo] LO(dotp), [dot_hi] HI(dotp), [k_lo] LO(kp), [k_hi] HI(kp), [v_lo] LO(vp), [v_hi] HI(vp),
+                 [lse_lo] LO(lsep), [lse_hi] HI(lsep), [dl_lo] LO(dlp), [dl_hi] HI(dlp), [dk_lo] LO(dkp), [dk_hi] HI(dkp),
+                 [dv_lo] LO(dvp), [dv_hi] HI(dvp), [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)), [cs] "s"(g.scale_log2e),
+                 [scale] "s"(g.scale), [nis] "s"(g.neg_inv_scale), [nloop] "s"((nq - 4) >> 1), [qmax] "s"((nq - 1) * 8192),
+                 [ldo32] "s"((int)(g.ldo * 64)), [cmax] "s"((nq - 1) * 128), [qk] "s"(qk), [klast] "s"(klast)
+               : ATTN_BWD_DKV64KV_CLOBBERS);
+#undef LO
+#undef HI
+}
+
 }  // namespace
 
 // Which backward kernels a problem gets: 1 = the generated 64-wide pair, 0 = the 8-wave pair.  The ONE predicate of mgx_attn_bwd
@@ -613,4 +739,43 @@ extern "C" int mgx_attn_bwd(const uint16_t* Q, const uint16_t* K, const uint16_t
 extern "C" int mgx_attn_bwd_path(int B, int H, int S, int Sp, long ldo, long o_bstride) {
   MGX_REQUIRE(B > 0 && H > 0 && S > 0 && Sp >= S && Sp % 64 == 0, "bad sizes");
   return attn_bwd_wide(B, H, S, Sp, ldo, o_bstride) ? 1 : 0;
+}
+
+// The masked-tail backward takes a problem when the 64-wide pair takes it at S = Sp = Sa and kv_len lies in the last 256 rows.
+// The ONE predicate of mgx_attn_bwd_kv and of the mgx_attn_bwd_kv_path query.  There is no other kernel behind it.
+static bool attn_bwd_kv_wide(int B, int H, int Sa, int kv_len, long ldo, long o_bstride) {
+  return B > 0 && H > 0 && Sa > 0 && kv_len > Sa - 256 && kv_len <= Sa && o_bstride >= (long)Sa * ldo &&
+         attn_bwd_wide(B, H, Sa, Sa, ldo, o_bstride);
+}
+
+extern "C" int mgx_attn_bwd_kv(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* Qt, const uint16_t* Kt,
+                               const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt,
+                               uint16_t* dQ, uint16_t* dK, uint16_t* dV, int B, int H, int Sa, int kv_len, long ldo,
+                               long o_bstride, float scale, void* stream) {
+  MGX_REQUIRE(Q && K && V && Qt && Kt && O && dO && lse && delta && dOt && dQ && dK && dV, "null operand");
+  MGX_REQUIRE(ldo % 8 == 0 && o_bstride % 8 == 0, "dO rows must be 16-byte aligned");
+  if (!attn_bwd_kv_wide(B, H, Sa, kv_len, ldo, o_bstride)) return 1;   // nothing launched: the caller's unpadded path
+  hipStream_t st = (hipStream_t)stream;
+  attn_bwd_prep_kv_kernel<<<dim3(Sa / 64, H, B), 256, 0, st>>>(O, dO, ldo, o_bstride, delta, dOt, H, Sa, kv_len);
+  BwdKvArgs a;
+  BwdArgs& g = a.g;
+  g.Q = Q; g.K = K; g.V = V; g.Qt = Qt; g.Kt = Kt; g.dO = dO; g.dOt = dOt; g.lse = lse; g.delta = delta;
+  g.dQ = dQ; g.dK = dK; g.dV = dV; g.B = B; g.H = H; g.S = Sa; g.Sp = Sa; g.ldo = ldo; g.o_bstride = o_bstride;
+  g.scale = scale; g.scale_log2e = scale * 1.4426950408889634f; g.neg_inv_scale = -1.0f / scale;
+  a.kv_len = kv_len;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dq64kv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv64kv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 149504);
+    attr = true;
+  }
+  const int nb = (Sa / 256) * H * B;
+  attn_bwd_dkv64kv_kernel<<<nb, 256, 149504, st>>>(a);
+  attn_bwd_dq64kv_kernel<<<nb, 256, 98304, st>>>(a);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int mgx_attn_bwd_kv_path(int B, int H, int Sa, int kv_len, long ldo, long o_bstride) {
+  return attn_bwd_kv_wide(B, H, Sa, kv_len, ldo, o_bstride) ? 1 : 0;
 }

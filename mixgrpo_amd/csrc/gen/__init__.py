@@ -6,6 +6,8 @@ import os
 import sys
 
 GENERATORS = ("attn_fwd64", "attn_bwd_dq64", "attn_bwd_dkv64")
+# (each generator's write() keeps all of its bodies current; the backward's two masked-tail bodies, *kv_body.inc, are build
+# products that only build._generate() writes -- .gitignore --, the others are committed)
 
 
 def generators():

@@ -25,10 +25,29 @@ iterations ahead (Q | dO, lse | delta) so that the first fragments of an iterati
 The `s_waitcnt lgkmcnt` in front of each MFMA is derived from the in-order LDS queue by the generator.
 Checked on the CPU by tests/test_attn_bwd64_emulated.py (interpreter + hazard pass) before it runs on a GPU.
 
+Masked tail (`kv`, attn_bwd_dkv64kv_body.inc, entry point mgx_attn_bwd_kv): the same stream for a sequence that was padded to a
+multiple of 256.  Everything is allocated at Sa; keys and queries >= kv_len (Sa - 256 < kv_len <= Sa) are padding that may hold
+any finite values.  The loop pays nothing -- its text is the unmasked stream's line for line:
+  * trailing 32-query blocks without a valid query are dropped by the launcher (`kv_operands`: nloop, qmax, cmax) in PAIRS,
+    64 queries, never below four blocks: the loop is unrolled by two for the Q^T | dO^T slots, and that is the only constraint
+    -- the Q | dO (3) and lse | delta (4) slots rotate in registers from block 0 of every launch, whatever the count;
+  * the loop runs one trip less and its last pair is emitted once more behind it.  Every iteration OUTSIDE the loop (the first,
+    the peeled pair, the last: four 32-query blocks) carries the mask: of a query >= kv_len, S' becomes -inf in front of
+    p = exp2(c S') -- P exactly 0 -- and dP' becomes 0 in front of ds = p dP' -- dS exactly 0 --, one v_cmp + one v_cndmask
+    each (`mask_query`; register e of a chain is query 16 (e >> 3) + 8 h + (e & 7) of the block, so the threshold is per lane
+    half).  SELECTS, not products: whatever the padding rows of Q, dO, lse made of S' and dP' is discarded, and 0 x (a finite
+    padding column of Q^T; dO^T's are zero) adds nothing to dK, dV.  With four blocks walked these are all there is;
+    otherwise the masked queries lie in the last two blocks that remain;
+  * a padding KEY (the key is on the lane: nothing it holds can reach another key's column) reads row kv_len - 1 of K and V
+    instead of its own, so that its accumulators stay finite, and the epilogue multiplies its dV by 0 instead of 1, its dK by
+    0 instead of `scale`: rows >= kv_len of dK, dV are stored as zero, by waves that own only padding keys too.
+kv_len = Sa masks nothing and gives the unmasked stream's bits.  Checked on the CPU by tests/test_attn_bwd64kv_emulated.py.
+
 What every stream needs alike (line buffer, counted loop, lane decode and pi(r), the LDS-DMA idiom, the store block, the .inc
 text) comes from csrc/gen/emit.py; this kernel's tile images are its own (32-query tiles, 64-byte transposed rows).
 """
 import os
+import sys
 from collections import namedtuple
 
 import emit
@@ -44,7 +63,8 @@ RING = 180                       # 12 fragment slots
 QB, QB0, VPRIV, TA, CB, CB0 = 228, 229, 230, 231, 233, 234      # TA: two registers (s2 = 0, 1)
 QSRC, DOSRC, TSRC, CSRC = 235, 237, 239, 241                     # 2, 2, 2 registers and a 64-bit pair
 T = 243                          # 8 Q / dO fragment addresses of the coming A phase
-X = 252                          # v[252:255]: short-lived scratch (even: 64-bit address pairs)
+X = 252                          # v[252:253]: short-lived scratch (a 64-bit address pair)
+NINF, THR = 254, 255             # kv: -inf; the lane threshold of the masked iteration under way (mask_query)
 V_LAST = 255
 
 sW, sWOFF2 = 60, 61              # wave id, w * 2048
@@ -54,6 +74,8 @@ sQ, sDO, sQT, sDOT = 80, 82, 84, 86           # tensor bases (pairs)
 sSP2, sLDO2, sCS, sSCALE, sNIS, sNLOOP, sQMAX, sLDO32, sCMAX = 88, 89, 90, 91, 92, 93, 94, 95, 96
 sDK, sDV = 62, 64                # epilogue: the DMA pointers' registers
 S_FIRST, S_LAST = 60, 97
+sQK = 56                         # kv: s[56:59] = 8 + the valid queries (0 .. 32) of the four blocks outside the loop
+S_FIRST_KV = 56
 
 QDO_SLOT = 16384
 T_BASE, C_BASE, VP_BASE = 49152, 81920, 83968
@@ -148,8 +170,16 @@ class LdsQueue:
             self.done = idx
 
 
-def valu_of_gap(g, first, last):
-    """VALU instructions of gap g of the steady-state iteration (see the module docstring)."""
+def mask_query(reg, i, sel):
+    """kv: register i (0 .. 15) of a chain's S' / dP' is query 16 (i >> 3) + 8 h + (i & 7) of the block (h = lane half); THR
+    holds 8 + (valid queries of the block, 0 .. 32) - 8 h, so `reg` becomes `sel` (-inf, 0) unless 8 + 16 (i >> 3) + (i & 7) < THR.
+    Unsigned on both sides by construction (the 8)."""
+    return [f"v_cmp_lt_u32 vcc, {8 + 16 * (i >> 3) + (i & 7)}, {v(THR)}", f"v_cndmask_b32 {reg}, {sel}, {reg}, vcc"]
+
+
+def valu_of_gap(g, first, last, masked=False):
+    """VALU instructions of gap g of the steady-state iteration (see the module docstring).
+    masked (kv, outside the loop): S' and dP' of the padding queries are replaced in front of their first VALU use."""
     out = []
 
     def sreg(e):
@@ -164,6 +194,8 @@ def valu_of_gap(g, first, last):
             out.append(f"v_xor_b32 {v(C + i)}, 0x80000000, {v(C + i)}")
     if 32 <= g <= 48:                                  # p = exp2(c S') in place: two elements per gap, exp one gap behind
         j = g - 32
+        if j < 16 and masked:
+            out += mask_query(sreg(2 * j), (2 * j) & 15, v(NINF)) + mask_query(sreg(2 * j + 1), (2 * j + 1) & 15, v(NINF))
         if j < 16:
             out.append(f"v_mul_f32 {sreg(2 * j)}, {sreg(2 * j)}, {s(sCS)}")
             out.append(f"v_mul_f32 {sreg(2 * j + 1)}, {sreg(2 * j + 1)}, {s(sCS)}")
@@ -175,6 +207,8 @@ def valu_of_gap(g, first, last):
         for k in ks_:
             ch, kk = CHAINS[k >> 3], k & 7
             out.append(f"v_cvt_pk_bf16_f32 {v(ch.P + kk)}, {v(ch.S + 2 * kk)}, {v(ch.S + 2 * kk + 1)}")
+            if masked:
+                out += mask_query(v(ch.DP + 2 * kk), 2 * kk, 0) + mask_query(v(ch.DP + 2 * kk + 1), 2 * kk + 1, 0)
             out.append(f"v_mul_f32 {v(ch.DP + 2 * kk)}, {v(ch.S + 2 * kk)}, {v(ch.DP + 2 * kk)}")
             out.append(f"v_mul_f32 {v(ch.DP + 2 * kk + 1)}, {v(ch.S + 2 * kk + 1)}, {v(ch.DP + 2 * kk + 1)}")
     if not last:
@@ -246,9 +280,15 @@ def c_dma(A):
     A.e(f"s_add_u32 {s(sCOFF)}, {s(sCOFF)}, 128")
 
 
-def emit_iteration(A, par, first=False, last=False):
-    """Iteration i (i & 1 == par): A(i), then B(i-1) under VALU(i) [first: no B(i-1)]."""
-    A.c(f"================ iteration parity {par}{' FIRST' if first else ''}{' LAST' if last else ''}")
+def emit_iteration(A, par, first=False, last=False, cnt=None):
+    """Iteration i (i & 1 == par): A(i), then B(i-1) under VALU(i) [first: no B(i-1)].
+    cnt (kv, outside the loop): the SGPR of 8 + the block's valid queries; the iteration carries the query mask."""
+    A.c(f"================ iteration parity {par}{' FIRST' if first else ''}{' LAST' if last else ''}"
+        f"{' MASKED' if cnt else ''}")
+    if cnt:
+        A.e(f"v_and_b32 {v(THR)}, 32, %[tid]")
+        A.e(f"v_lshrrev_b32 {v(THR)}, 2, {v(THR)}")                         # 8 * lane half
+        A.e(f"v_sub_u32 {v(THR)}, {s(cnt)}, {v(THR)}")
     Q = LdsQueue(A)
     # issued at the end of the previous iteration (or of the prologue), in this order: C0, then the fragments used before LEAD
     pre = sorted((f for f in PLAN if PLAN[f][1] - LEAD < 0), key=lambda f: PLAN[f][1])
@@ -277,7 +317,7 @@ def emit_iteration(A, par, first=False, last=False):
             Q.need([("c1",)])
         if g == 44 and not last:
             Q.need([("c0n",)])
-        fill = valu_of_gap(g, first, last)
+        fill = valu_of_gap(g, first, last, masked=cnt is not None)
         if g in dmas:
             m0w, ld = dmas[g]
             if m0w.startswith(f"s_add_i32 m0, {s(sQDST)}"):    # Q | dO pieces: m0 = rotating slot + w * 2048 + piece
@@ -304,7 +344,7 @@ def emit_iteration(A, par, first=False, last=False):
 
 
 # ------------------------------------------------------------------------------------------------ prologue / epilogue
-def prologue(A):
+def prologue(A, kv=False):
     for nm, reg in (("q", sQ), ("do", sDO), ("qt", sQT), ("dot", sDOT)):
         A.e(f"s_mov_b32 {s(reg)}, %[{nm}_lo]")
         A.e(f"s_mov_b32 {s(reg + 1)}, %[{nm}_hi]")
@@ -368,13 +408,26 @@ def prologue(A):
     A.c("K fragments (B operands) and the V fragments' DMA: row 32 c + r of this wave's 64 keys, chunk 2 ks + h")
     koff = v(RING + 10)
     A.e(f"v_lshl_add_u32 {t0}, {w}, 6, {r}")
+    if kv:
+        A.c("masked tail: a padding key reads row %[klast] (the block's last valid key) of K and V instead of its own")
+        A.e(f"v_add_u32 {t1}, 32, {t0}")
+        A.e(f"v_min_u32 {t0}, %[klast], {t0}")
+        A.e(f"v_min_u32 {t1}, %[klast], {t1}")
+        A.e(f"v_lshlrev_b32 {t1}, 8, {t1}")
+        A.e(f"v_lshl_add_u32 {v(RING + 11)}, {h}, 4, {t1}")
+        A.c("%[qk] = four bytes, 8 + the valid queries (0 .. 32) of the first block and of the last three; -inf")
+        for i in range(4):
+            A.e(f"s_lshr_b32 {s(sQK + i)}, %[qk], {8 * i}")
+            A.e(f"s_and_b32 {s(sQK + i)}, {s(sQK + i)}, 0xff")
+        A.e(f"v_mov_b32 {v(NINF)}, 0xff800000")
     A.e(f"v_lshlrev_b32 {t0}, 8, {t0}")
     A.e(f"v_lshl_add_u32 {koff}, {h}, 4, {t0}")
     A.e(f"s_mov_b32 {s(sQP)}, %[k_lo]")
     A.e(f"s_mov_b32 {s(sQP + 1)}, %[k_hi]")
     A.e(f"s_mov_b32 {s(sDOP)}, %[v_lo]")
     A.e(f"s_mov_b32 {s(sDOP + 1)}, %[v_hi]")
-    A.e(f"v_add_u32 {v(RING + 11)}, 8192, {koff}")
+    if not kv:
+        A.e(f"v_add_u32 {v(RING + 11)}, 8192, {koff}")
     for ci, ch in enumerate(CHAINS):
         for ks in range(8):
             A.e(f"global_load_dwordx4 {vr(ch.KF + 4 * ks, 4)}, {v(RING + 10 + ci)}, {sr(sQP, 2)} offset:{32 * ks}")
@@ -421,7 +474,7 @@ def prologue(A):
         A.e(f"v_mul_f32 {v(C + i)}, {v(C + i)}, {s(sNIS)}")
 
 
-def epilogue(A):
+def epilogue(A, kv=False):
     A.c("================ tail: dS of the last block, then B(last) alone")
     for k in range(16):
         ch, kk = CHAINS[k >> 3], k & 7
@@ -440,6 +493,18 @@ def epilogue(A):
     L = emit.lane_decode(A, RING)
     w, r, h, t0, off_a, off_b = L.w, L.r, L.h, L.t0, v(RING + 5), v(RING + 6)
     A.e(f"v_lshl_add_u32 {t0}, {w}, 6, {r}")
+    mv, mk = (None, None), (s(sSCALE), s(sSCALE))
+    if kv:                                                                  # multipliers, 0 in the lanes of a padding key
+        one, scl, zero, rb = (v(RING + 36 + i) for i in range(4))
+        mv, mk = (v(RING + 32), v(RING + 33)), (v(RING + 34), v(RING + 35))
+        A.e(f"v_mov_b32 {one}, 0x3f800000")                              # 1.0
+        A.e(f"v_mov_b32 {scl}, {s(sSCALE)}")
+        A.e(f"v_mov_b32 {zero}, 0")
+        A.e(f"v_add_u32 {rb}, 32, {t0}")
+        for c, row in ((0, t0), (1, rb)):
+            A.e(f"v_cmp_lt_u32 vcc, %[klast], {row}")
+            A.e(f"v_cndmask_b32 {mv[c]}, {one}, {zero}, vcc")
+            A.e(f"v_cndmask_b32 {mk[c]}, {scl}, {zero}, vcc")
     A.e(f"v_lshlrev_b32 {t0}, 8, {t0}")
     A.e(f"v_lshl_add_u32 {off_a}, {h}, 4, {t0}")
     A.e(f"v_add_u32 {off_b}, 8192, {off_a}")
@@ -448,34 +513,52 @@ def epilogue(A):
     A.e(f"s_mov_b32 {s(sDV)}, %[dv_lo]")
     A.e(f"s_mov_b32 {s(sDV + 1)}, %[dv_hi]")
     # 4 staging quads RING+8 .. RING+23, 8 read registers RING+24 .. +31
-    for acc, ptr, mul, off in ((DV_A, sDV, None, off_a), (DV_B, sDV, None, off_b),
-                               (DK_A, sDK, s(sSCALE), off_a), (DK_B, sDK, s(sSCALE), off_b)):
+    for acc, ptr, mul, off in ((DV_A, sDV, mv[0], off_a), (DV_B, sDV, mv[1], off_b),
+                               (DK_A, sDK, mk[0], off_a), (DK_B, sDK, mk[1], off_b)):
         emit.store_acc_bf16(A, acc, mul, RING + 8, RING + 24, off, ptr)
 
 
-def generate():
+def generate(kv=False):
     A = Asm()
-    prologue(A)
+    cnt = (lambda i: sQK + i) if kv else (lambda i: None)
+    prologue(A, kv)
     for fid in sorted((f for f in PLAN if PLAN[f][1] - LEAD < 0), key=lambda f: PLAN[f][1]):
         A.e(read_instr(fid, 0))
-    emit_iteration(A, 0, first=True)
+    emit_iteration(A, 0, first=True, cnt=cnt(0))
     emit.counted_loop(A, sLOOP, sNLOOP, lambda: emit_iteration(A, 1), lambda: emit_iteration(A, 0))
-    emit_iteration(A, 1, last=True)
-    epilogue(A)
+    if kv:                                               # the loop runs one trip less: its last pair is peeled
+        emit_iteration(A, 1, cnt=cnt(1))
+        emit_iteration(A, 0, cnt=cnt(2))
+    emit_iteration(A, 1, last=True, cnt=cnt(3))
+    epilogue(A, kv)
     return A.text()
+
+
+def kv_operands(kv_len, kt=0):
+    """kv: what the launcher derives from kv_len for the workgroup of key block `kt` (csrc/attention_bwd.hip restates it; the
+    CPU tests feed the interpreter from here): the 32-query blocks walked -- those with a valid query, rounded up to a pair, at
+    least four --, the loop's trips (its last pair is peeled), the clamps of the Q | dO and lse | delta fetches, qk = four
+    bytes, lowest first: 8 + the valid queries (0 .. 32) of the first block and of the last three, and the block's last valid
+    key row."""
+    nq = max(4, ((kv_len + 31) // 32 + 1) & ~1)
+    c = lambda i: 8 + min(32, max(0, kv_len - 32 * i))
+    return dict(nloop=(nq - 4) // 2, qmax=(nq - 1) * 8192, cmax=(nq - 1) * 128,
+                qk=c(0) | c(nq - 3) << 8 | c(nq - 2) << 16 | c(nq - 1) << 24, klast=min(255, kv_len - 1 - 256 * kt))
 
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_BODY = os.path.join(HERE, "..", "attn_bwd_dkv64_body.inc")
+OUT_BODY_KV = os.path.join(HERE, "..", "attn_bwd_dkv64kv_body.inc")
 
 
-def render():
-    return emit.render("ATTN_BWD_DKV64", __file__, generate(), emit.clobbers(V_LAST, S_FIRST, S_LAST))
+def render(kv=False):
+    return emit.render("ATTN_BWD_DKV64KV" if kv else "ATTN_BWD_DKV64", __file__, generate(kv),
+                       emit.clobbers(V_LAST, S_FIRST_KV if kv else S_FIRST, S_LAST))
 
 
-def write(path=OUT_BODY):
-    return emit.write_if_changed(path, render())
+def write():
+    return tuple(emit.write_if_changed(path, render(kv)) for path, kv in ((OUT_BODY, False), (OUT_BODY_KV, True)))
 
 
 if __name__ == "__main__":
-    emit.main(generate, write)
+    emit.main(lambda: generate("--kv" in sys.argv), write)

@@ -21,8 +21,25 @@ tile ([128 d][64 keys], the forward's V^T image), by LDS-DMA.  Barrier interval 
 tile t (keys 64 t ..) and the K / V WINDOW of keys 64 t + 32 .. 64 t + 95 (QK runs one block ahead of DQ); the window's
 second half does not exist in the last interval: waves 2, 3, whose DMA pieces it is, skip them.
 dQ is scaled by `scale` in the epilogue (dS carries no scale).  Checked on the CPU by tests/test_attn_bwd64_emulated.py.
+
+Masked tail (`kv`, attn_bwd_dq64kv_body.inc, entry point mgx_attn_bwd_kv): the same stream for a sequence that was padded to a
+multiple of 256.  Everything is allocated at Sa; keys and queries >= kv_len (Sa - 256 < kv_len <= Sa) are padding that may hold
+any finite values.  The loop pays nothing -- its text is the unmasked stream's line for line:
+  * trailing key tiles without a valid key are dropped in pairs by the launcher (`kv_operands`: nloop, seq), never below four;
+  * the loop runs one trip less and its last pair of intervals is emitted once more behind it.  Every interval OUTSIDE the loop
+    (the first, the peeled pair, the last: eight 32-key blocks) carries the mask in its softmax stream: dS of a key >= kv_len
+    is replaced by 0 behind `ds = p (dp - delta)`, one v_cmp + one v_cndmask per element (`mask_key`; S register e of a block is
+    key 16 (e >> 3) + 8 h + (e & 7), so the threshold is per lane half, v[248:255]).  A SELECT, not a product: whatever the
+    padding rows of K and V made of p and dp -- inf, NaN -- is discarded, and 0 x (a finite K^T padding column) adds nothing to
+    dQ.  With four tiles walked (Sa = 256, or kv_len within the first 256 keys) these eight blocks are all there is, so no
+    further mask block is needed; otherwise the masked keys lie in the last two tiles that remain;
+  * a padding QUERY row (the query is on the lane: nothing it holds can reach another row) reads row kv_len - 1 of Q, dO, lse
+    and delta instead of its own, so that its accumulators stay finite, and its dQ is multiplied by 0 instead of `scale` in
+    the epilogue (v245, v246): rows >= kv_len of dQ are stored as zero.
+kv_len = Sa masks nothing and gives the unmasked stream's bits.  Checked on the CPU by tests/test_attn_bwd64kv_emulated.py.
 """
 import os
+import sys
 from collections import namedtuple
 
 import emit
@@ -44,6 +61,9 @@ LSE_A, LSE_B, DL_A, DL_B = 208, 209, 210, 211
 X = 212             # v[212:243] scratch (prologue / epilogue)
 ROWOFF = 244        # (w * 64 + r) * 256 + h * 16: Q / dQ byte offset of this lane
 V_LAST = 247
+SCL_A, SCL_B = 245, 246   # kv: `scale`, or 0 in the lanes of a padding query row (the epilogue's multiplier)
+TH = 248            # kv: v[248:255] lane thresholds of the eight 32-key blocks outside the loop (mask_key)
+V_LAST_KV = 255
 
 sW, sWOFF = 64, 65
 sKP, sVP, sKTP = 66, 68, 70      # pairs: DMA base pointers
@@ -96,8 +116,17 @@ def read_kt(n, slot, kb):
     return f"ds_read_b128 {vr(KTF + 4 * n, 4)}, {v(KTA + 2 * kb + s2)} offset:{slot * SLOT + dt * 4096}"   # KT_BASE in the address
 
 
-def softmax_stream(ch):
-    """SM(c, j) as a flat, software-pipelined instruction list (72 instructions, 16 of them v_exp_f32)."""
+def mask_key(ch, e, thr):
+    """kv: S / dP register e of a chain is key 16 (e >> 3) + 8 h + (e & 7) of the 32-key block (h = lane half); `thr` (a VGPR)
+    holds 8 + (valid keys of the block, 0 .. 32) - 8 h, so the key's dS -- in its dP register -- becomes 0 unless
+    8 + 16 (e >> 3) + (e & 7) < thr.  Unsigned on both sides by construction (the 8)."""
+    return [f"v_cmp_lt_u32 vcc, {8 + 16 * (e >> 3) + (e & 7)}, {thr}",
+            f"v_cndmask_b32 {v(ch.DP + e)}, 0, {v(ch.DP + e)}, vcc"]
+
+
+def softmax_stream(ch, thr=None):
+    """SM(c, j) as a flat, software-pipelined instruction list (72 instructions, 16 of them v_exp_f32).
+    kv, outside the loop: thr = the VGPR of the block's lane threshold, dS of the masked keys is replaced by 0 (+ 32)."""
     def t(e):
         return v(T + (e & 7))
     out = []
@@ -110,6 +139,8 @@ def softmax_stream(ch):
             out.append(f"v_sub_f32 {v(ch.DP + e)}, {v(ch.DP + e)}, {v(ch.DL)}")
         if 0 <= e - 2 < 16:
             out.append(f"v_mul_f32 {v(ch.DP + e - 2)}, {t(e - 2)}, {v(ch.DP + e - 2)}")
+            if thr is not None:
+                out += mask_key(ch, e - 2, thr)
         if 0 <= e - 3 < 16 and ((e - 3) & 1):
             k = (e - 3) >> 1
             out.append(f"v_cvt_pk_bf16_f32 {v(ch.DS + k)}, {v(ch.DP + 2 * k)}, {v(ch.DP + 2 * k + 1)}")
@@ -123,13 +154,14 @@ def dma_piece(kind, p, slot, ptrs=None):
     return (f"s_add_i32 m0, {s(sWOFF)}, {base}", f"global_load_lds_dwordx4 {v(src)}, {sr(ptr, 2)}")
 
 
-def block_iteration(A, par, kb, first=False, last=False, dma1=None, dma2=None):
+def block_iteration(A, par, kb, first=False, last=False, dma1=None, dma2=None, thr=None):
     """Block-iteration j = 2 t + kb, t & 1 == par.  K, V (j+1) live in window half kb of slot par; K^T (j) in tile half kb.
-    dma1 / dma2: DMA pieces issued inside segment 1 / segment 2."""
-    A.c(f"================ block-iteration parity {par} kb {kb}{' FIRST' if first else ''}{' LAST' if last else ''}")
+    dma1 / dma2: DMA pieces issued inside segment 1 / segment 2.  thr (kv, outside the loop): the block's mask threshold."""
+    A.c(f"================ block-iteration parity {par} kb {kb}{' FIRST' if first else ''}{' LAST' if last else ''}"
+        f"{' MASKED' if thr else ''}")
     # ---------------- segment 1: QK(b, j), DQ(b, j-1); SM(a, j); K, V (j+1) reloads
     mf = [mfma_qk(CB, g) for g in range(16)] + ([] if first else [mfma_dq(CB, n) for n in range(8)])
-    vg = spread(softmax_stream(CA), len(mf))
+    vg = spread(softmax_stream(CA, thr), len(mf))
     lds = {} if last else {g: read_kv(g, par, kb) for g in range(16)}
     dma = {1 + 3 * i: pc for i, pc in enumerate(dma1 or [])}
     A.c("---- segment 1")
@@ -138,7 +170,7 @@ def block_iteration(A, par, kb, first=False, last=False, dma1=None, dma2=None):
         A.e("s_nop 3")                                      # no DQ gaps behind QK(b, 0): its dP is read by the next VALU
     # ---------------- segment 2: QK(a, j+1), DQ(a, j); SM(b, j); K^T (j) reloads
     mf = ([] if last else [mfma_qk(CA, g) for g in range(16)]) + [mfma_dq(CA, n) for n in range(8)]
-    vg = spread(softmax_stream(CB), len(mf))
+    vg = spread(softmax_stream(CB, thr), len(mf))
     lds = {n: read_kt(n, par, kb) for n in range(8)}
     waits = {0: "s_waitcnt lgkmcnt(0)", 16: "s_waitcnt lgkmcnt(0)"}
     if last:                                                 # K^T reads, then DQ at once: read first, wait, then the MFMAs
@@ -150,12 +182,13 @@ def block_iteration(A, par, kb, first=False, last=False, dma1=None, dma2=None):
     emit.segment(A, mf, vg, lds=lds, dma=dma, waits=waits)
 
 
-def interval(A, par, first=False, last=False):
-    """Barrier interval t (t & 1 == par): block-iterations (2t, 2t+1) + the DMA of interval t+1's tiles."""
+def interval(A, par, first=False, last=False, th=(None, None)):
+    """Barrier interval t (t & 1 == par): block-iterations (2t, 2t+1) + the DMA of interval t+1's tiles.
+    th (kv, outside the loop): the mask thresholds of its two blocks."""
     nxt = 1 - par
     if last:
-        block_iteration(A, par, 0, first=first)
-        block_iteration(A, par, 1, last=True)
+        block_iteration(A, par, 0, first=first, thr=th[0])
+        block_iteration(A, par, 1, last=True, thr=th[1])
         return
     kt = [dma_piece("kt", p, nxt) for p in range(4)]
     kp = [dma_piece("k", p, nxt) for p in range(4)]
@@ -169,8 +202,8 @@ def interval(A, par, first=False, last=False):
     for dst, src in ((sKPU, sKP), (sVPU, sVP)):
         A.e(f"s_sub_u32 {s(dst)}, {s(src)}, {s(sTMP)}")
         A.e(f"s_subb_u32 {s(dst + 1)}, {s(src + 1)}, 0")
-    block_iteration(A, par, 0, first=first, dma1=kp, dma2=kt[:2])
-    block_iteration(A, par, 1, dma1=vp, dma2=kt[2:])
+    block_iteration(A, par, 0, first=first, dma1=kp, dma2=kt[:2], thr=th[0])
+    block_iteration(A, par, 1, dma1=vp, dma2=kt[2:], thr=th[1])
     A.e(f"s_add_u32 {s(sKTT)}, {s(sKTT)}, 128")                             # next K^T tile: + 64 keys
     A.e(f"s_add_u32 {s(sROW)}, {s(sROW)}, 64")
     A.e(f"s_add_u32 {s(sKP)}, {s(sKP)}, {SLOT}")                            # next window: + 64 rows of 256 bytes
@@ -182,7 +215,7 @@ def interval(A, par, first=False, last=False):
 
 
 # ------------------------------------------------------------------------------------------------ prologue / epilogue
-def prologue(A):
+def prologue(A, kv=False):
     names = (("q", sQ), ("k", sK), ("v", sV), ("kt", sKT), ("do", sDO), ("lse", sLSE), ("dl", sDL), ("dq", sDQ))
     for nm, reg in names:
         A.e(f"s_mov_b32 {s(reg)}, %[{nm}_lo]")
@@ -211,6 +244,34 @@ def prologue(A):
     A.e(f"s_lshl_b32 {s(sTMP)}, {s(sLDO2)}, 5")
     A.e(f"v_add_u32 {v(X + 13)}, {s(sTMP)}, {v(X + 12)}")                  # dO offset chain b
     A.e(f"v_lshlrev_b32 {v(X + 14)}, 2, {row}")                            # lse / delta offset
+    qa, qb, doa, dob, la, lb = ROWOFF, X + 11, X + 12, X + 13, X + 14, None
+    if kv:
+        A.c("masked tail: a padding query row reads row %[qlast] (the block's last valid row) of Q / dO / lse / delta instead of")
+        A.c("its own and multiplies its dQ by 0; ROWOFF stays the lane's own row (the dQ store)")
+        ra, rb, vs, vz = v(X + 15), v(X + 16), v(X + 17), v(X + 18)
+        qa, lb = X + 19, X + 20
+        A.e(f"v_add_u32 {rb}, 32, {row}")
+        A.e(f"v_mov_b32 {vs}, {s(sSCALE)}")
+        A.e(f"v_mov_b32 {vz}, 0")
+        A.e(f"v_cmp_lt_u32 vcc, %[qlast], {row}")
+        A.e(f"v_cndmask_b32 {v(SCL_A)}, {vs}, {vz}, vcc")
+        A.e(f"v_cmp_lt_u32 vcc, %[qlast], {rb}")
+        A.e(f"v_cndmask_b32 {v(SCL_B)}, {vs}, {vz}, vcc")
+        A.e(f"v_min_u32 {ra}, %[qlast], {row}")
+        A.e(f"v_min_u32 {rb}, %[qlast], {rb}")
+        for rr, qo, do_, lo in ((ra, qa, doa, la), (rb, qb, dob, lb)):
+            A.e(f"v_lshlrev_b32 {t1}, 8, {rr}")
+            A.e(f"v_lshl_add_u32 {v(qo)}, {h}, 4, {t1}")
+            A.e(f"v_mul_lo_u32 {t1}, {rr}, {s(sLDO2)}")
+            A.e(f"v_lshl_add_u32 {v(do_)}, {h}, 4, {t1}")
+            A.e(f"v_lshlrev_b32 {v(lo)}, 2, {rr}")
+        A.c("lane thresholds of the eight 32-key blocks outside the loop: %[kt0], %[kt1] = four bytes each, 8 + the valid keys")
+        A.c("(0 .. 32) of the blocks of the first tile and of the last three (mask_key)")
+        A.e(f"v_lshlrev_b32 {t1}, 3, {h}")
+        for i in range(8):
+            A.e(f"s_lshr_b32 {s(sTMP)}, %[kt{i >> 2}], {8 * (i & 3)}")
+            A.e(f"s_and_b32 {s(sTMP)}, {s(sTMP)}, 0xff")
+            A.e(f"v_sub_u32 {v(TH + i)}, {s(sTMP)}, {t1}")
     A.c("first tiles: K^T tile 0 and the K / V window of keys 32..95 -> slot 0; keys 0..31 (the second half of 'window -1',")
     A.c("the pieces of waves 2 and 3, whose source rows are 32..63 of it) -> slot 1")
     A.e(f"s_mov_b32 {s(sKTT)}, 0")
@@ -243,15 +304,17 @@ def prologue(A):
     A.e(f"s_add_u32 {s(sVP)}, {s(sVP)}, {SLOT}")
     A.e(f"s_addc_u32 {s(sVP + 1)}, {s(sVP + 1)}, 0")
     A.c("Q and dO fragments (B operands), lse * log2(e) and delta of this lane's two rows")
-    for ch, qoff, dooff in ((CA, ROWOFF, X + 12), (CB, X + 11, X + 13)):
+    for ch, qoff, dooff in ((CA, qa, doa), (CB, qb, dob)):
         for ks in range(8):
             A.e(f"global_load_dwordx4 {ar(ch.QF + 4 * ks, 4)}, {v(qoff)}, {sr(sQ, 2)} offset:{32 * ks}")
         for ks in range(8):
             A.e(f"global_load_dwordx4 {ar(ch.DOF + 4 * ks, 4)}, {v(dooff)}, {sr(sDO, 2)} offset:{32 * ks}")
-    A.e(f"global_load_dword {v(LSE_A)}, {v(X + 14)}, {sr(sLSE, 2)}")
-    A.e(f"global_load_dword {v(LSE_B)}, {v(X + 14)}, {sr(sLSE, 2)} offset:128")
-    A.e(f"global_load_dword {v(DL_A)}, {v(X + 14)}, {sr(sDL, 2)}")
-    A.e(f"global_load_dword {v(DL_B)}, {v(X + 14)}, {sr(sDL, 2)} offset:128")
+    offb = " offset:128" if lb is None else ""
+    lb = la if lb is None else lb
+    A.e(f"global_load_dword {v(LSE_A)}, {v(la)}, {sr(sLSE, 2)}")
+    A.e(f"global_load_dword {v(LSE_B)}, {v(lb)}, {sr(sLSE, 2)}{offb}")
+    A.e(f"global_load_dword {v(DL_A)}, {v(la)}, {sr(sDL, 2)}")
+    A.e(f"global_load_dword {v(DL_B)}, {v(lb)}, {sr(sDL, 2)}{offb}")
     A.c("dQ = 0")
     for i in range(128):
         A.e(f"v_accvgpr_write_b32 {a(i)}, 0")
@@ -272,7 +335,7 @@ def prologue(A):
     A.e("s_nop 7")
 
 
-def epilogue(A):
+def epilogue(A, kv=False):
     A.c("================ tail: DQ(b) of the last block")
     for n in range(8):
         A.e(mfma_dq(CB, n))
@@ -280,31 +343,51 @@ def epilogue(A):
     A.e("s_nop 7")
     A.c("================ epilogue: dQ * scale -> bf16, 16-byte stores (lane halves exchanged pairwise)")
     for ch, addr in ((CA, ROWOFF), (CB, X + 7)):          # X + 7: chain b's rows, 32 further (generate())
-        emit.store_acc_bf16(A, ch.DQ, s(sSCALE), X + 8, X + 24, v(addr), sDQ)
+        mul = s(sSCALE) if not kv else v(SCL_A if ch is CA else SCL_B)      # kv: 0 in the lanes of a padding query row
+        emit.store_acc_bf16(A, ch.DQ, mul, X + 8, X + 24, v(addr), sDQ)
 
 
-def generate():
+def generate(kv=False):
     A = Asm()
-    prologue(A)
+    th = (lambda i: (v(TH + i), v(TH + i + 1))) if kv else (lambda i: (None, None))
+    prologue(A, kv)
     A.e(f"v_add_u32 {v(X + 7)}, 8192, {v(ROWOFF)}")     # chain b dQ offset for the epilogue (X + 7 is free from here on)
-    interval(A, 0, first=True)
+    interval(A, 0, first=True, th=th(0))
     emit.counted_loop(A, sLOOP, sNLOOP, lambda: interval(A, 1), lambda: interval(A, 0))
-    interval(A, 1, last=True)
-    epilogue(A)
+    if kv:                                               # the loop runs one trip less: its last pair is peeled
+        interval(A, 1, th=th(2))
+        interval(A, 0, th=th(4))
+    interval(A, 1, last=True, th=th(6))
+    epilogue(A, kv)
     return A.text()
+
+
+def kv_operands(kv_len, qt=0):
+    """kv: what the launcher derives from kv_len for the workgroup of q-tile `qt` (csrc/attention_bwd.hip restates it; the CPU
+    tests feed the interpreter from here): the 64-key tiles walked -- those with a valid key, rounded up to a pair, at least
+    four --, the loop's trips (its last pair is peeled), the length the window fetch is clamped at, kt0 / kt1 = four bytes
+    each, lowest first: 8 + the valid keys (0 .. 32) of the 32-key blocks of the first tile and of the last three, and the
+    block's last valid query row."""
+    nt = max(4, ((kv_len + 63) // 64 + 1) & ~1)
+    c = lambda j: 8 + min(32, max(0, kv_len - 32 * j))
+    pack = lambda js: sum(c(j) << (8 * i) for i, j in enumerate(js))
+    return dict(nloop=(nt - 4) // 2, seq=64 * nt, kt0=pack((0, 1, 2 * nt - 6, 2 * nt - 5)),
+                kt1=pack((2 * nt - 4, 2 * nt - 3, 2 * nt - 2, 2 * nt - 1)), qlast=min(255, kv_len - 1 - 256 * qt))
 
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_BODY = os.path.join(HERE, "..", "attn_bwd_dq64_body.inc")
+OUT_BODY_KV = os.path.join(HERE, "..", "attn_bwd_dq64kv_body.inc")
 
 
-def render():
-    return emit.render("ATTN_BWD_DQ64", __file__, generate(), emit.clobbers(V_LAST, S_FIRST, S_LAST))
+def render(kv=False):
+    return emit.render("ATTN_BWD_DQ64KV" if kv else "ATTN_BWD_DQ64", __file__, generate(kv),
+                       emit.clobbers(V_LAST_KV if kv else V_LAST, S_FIRST, S_LAST))
 
 
-def write(path=OUT_BODY):
-    return emit.write_if_changed(path, render())
+def write():
+    return tuple(emit.write_if_changed(path, render(kv)) for path, kv in ((OUT_BODY, False), (OUT_BODY_KV, True)))
 
 
 if __name__ == "__main__":
-    emit.main(generate, write)
+    emit.main(lambda: generate("--kv" in sys.argv), write)

@@ -4,8 +4,9 @@ A generator holds what is specific to its kernel -- design, register map, MFMA /
 from the emitters here, each of which exists once: register names and the line buffer `Asm`; the counted loop; the lane
 decode and the tile images' address set-ups; the LDS-DMA idiom and the MFMA-gap `segment`; the accumulator -> bf16 store
 block; `render` (stream -> the C macros of a *_body.inc) and the command line.  Nothing here knows a register map: every
-register and operand is an argument, so an emitter reproduces each of its users' streams exactly (the .inc files are
-committed, and a CPU test interprets them).  Plain module, no imports from the package: the generators run as scripts.
+register and operand is an argument, so an emitter reproduces each of its users' streams exactly (the unmasked and the
+forward's .inc files are committed, the backward's two masked-tail bodies are written by the build only; CPU tests interpret
+the generators' text).  Plain module, no imports from the package: the generators run as scripts.
 """
 import os
 import sys

@@ -199,7 +199,7 @@ class _Work:
     slices of it (`view`), so the rollout (B = G), the shared first step (B = 1) and the replay micro-batches share one
     allocation instead of one per batch size."""
 
-    kv_len = None     # set by the padded no-grad forward for the length of one call: the keys >= kv_len of S are padding
+    kv_len = None     # set by a padded forward / backward (ops.ATTN_PAD_KV) for the length of one call: rows >= kv_len of S are padding
 
     def __init__(self, cfg, B, L, N, device):
         d, H, hd = cfg.dim, cfg.num_attention_heads, cfg.attention_head_dim
@@ -283,6 +283,8 @@ class FluxTransformer2DModel(torch.nn.Module):
         self.recompute = True
         self.last_route = None                    # of the last no-grad forward: "plain" | "padded_kv" (ops.ATTN_PAD_KV)
         self.padded_kv_calls = 0
+        self.last_train_route = None              # of the last training forward (FluxFunction): "plain" | "padded_kv"
+        self.padded_kv_train_calls = 0
 
     # ------------------------------------------------------------------ parameters / checkpoints
     def state_dict(self, *args, **kwargs):
@@ -370,7 +372,8 @@ class FluxTransformer2DModel(torch.nn.Module):
             ops.attn_fp8_quantize(w.Q, w.K, w.Vt, q8, k8, v8t, amax, w.B, H, w.S, w.Sp)
             ops.attn_fwd_fp8(q8, k8, v8t, amax, O, lse, w.B, H, w.S, w.Sp, ldo, o_bstride, scale)
         elif ops.Q_PRESCALE and w.kv_len is not None:
-            # padded no-grad forward: every buffer is allocated at w.S (% 256 == 0), the image rows >= kv_len are padding
+            # padded forward (no-grad, training, recompute): every buffer is allocated at w.S (% 256 == 0), the image rows
+            # >= kv_len are padding
             if not ops.attn_fwd_log2_kv(w.Q, w.K, w.Vt, O, lse, w.B, H, w.S, w.kv_len, ldo, o_bstride):
                 raise MgxError(f"mgx_attn_fwd_log2_kv refused B {w.B} H {H} Sa {w.S} kv_len {w.kv_len} after its path query took it")
         elif ops.Q_PRESCALE:
@@ -655,7 +658,7 @@ class FluxTransformer2DModel(torch.nn.Module):
         """Image rows of the padded no-grad forward (ops.ATTN_PAD_KV), or None for the plain one: a sequence off 256 is run
         at the next multiple of 256 with the added keys masked (`mgx_attn_fwd_log2_kv`), so that the 64-query attention
         forward and the fused q | k / V^T projections take it (720 x 720: 512 + 2025 = 2537 -> 2560, image rows 2048).
-        Forward only: the training forward / backward / replay have no masked backward and keep the unpadded kernels."""
+        The training path asks `_pad_kv_rows_train`, which also needs the masked backward to take the shape."""
         S = L + N
         if not ops.ATTN_PAD_KV or S % 256 == 0 or not ops.Q_PRESCALE or self.attention_dtype != "bf16":
             return None
@@ -665,6 +668,20 @@ class FluxTransformer2DModel(torch.nn.Module):
         if not all(ops.attn_fwd_kv_path(B, H, Sa, S, ld, Sa * ld) == 1 for ld in (d, 5 * d)):
             return None
         return Sa - L
+
+    def _pad_kv_rows_train(self, B, L, N):
+        """Image rows of the padded TRAINING forward / recompute / backward (flux_backward.FluxFunction), or None for the plain
+        one: `_pad_kv_rows` and the masked attention backward (`mgx_attn_bwd_kv`) both take the shape.  The rollout and the
+        replay of a sample then run the same kernels on the same padded shape."""
+        N_pad = self._pad_kv_rows(B, L, N)
+        if N_pad is None:
+            return None
+        d, H = self.cfg.dim, self.cfg.num_attention_heads
+        Sa = L + N_pad
+        # (ldo, batch stride) of dO / O: the double blocks and lean single blocks, the single blocks' d(cat)
+        if not all(ops.attn_bwd_kv_path(B, H, Sa, L + N, ld, Sa * ld) == 1 for ld in (d, 5 * d)):
+            return None
+        return N_pad
 
     def _padded_inputs(self, hidden_states, img_ids, N_pad):
         """hidden_states [B, N, C] / img_ids [N, 3] with zero rows appended up to N_pad.  The padded ids are cached with the

@@ -176,32 +176,47 @@ class FluxFunction(torch.autograd.Function):
         cfg = model.cfg
         B, N, _ = hidden_states.shape
         L = encoder_hidden_states.shape[1]
-        w = model._workspace(B, L, N)
+        # ops.ATTN_PAD_KV: a sequence off 256 runs on the workspace of the next multiple, zero image rows appended, the rows
+        # >= kv_len masked in the attention forward (model._attn) and backward (_attn_bwd); kv_len is set on the workspace for
+        # the length of this call and of the backward only
+        N_pad = model._pad_kv_rows_train(B, L, N)
+        kv_len = None
+        if N_pad is not None:
+            hidden_states, img_ids = model._padded_inputs(hidden_states, img_ids, N_pad)
+            kv_len = L + N
+        w = model._workspace(B, L, N if N_pad is None else N_pad)
         tr = _train_buffers(cfg, w, model.store.device)
-        ehs = model._embed(w, hidden_states, encoder_hidden_states)
-        keep = {}
-        temb, st = model._temb(B, timestep.to(model.store.device), guidance, pooled_projections, keep=keep)
-        cos, sin = model._rope(txt_ids, img_ids)
-        mods = []
-        blk = 0
-        for i in range(cfg.num_layers):
-            tr.block_in[blk].copy_(w.X)
-            mods.append(model._double_block(i, w, st, cos, sin, keep=tr.keep[blk] if tr.keep else None))
-            blk += 1
-        for i in range(cfg.num_single_layers):
-            tr.block_in[blk].copy_(w.X)
-            mods.append(model._single_block(i, w, st, cos, sin, keep=tr.keep[blk] if tr.keep else None))
-            blk += 1
-        tr.x_final.copy_(w.X)
-        out, e = model._head(w, st)
+        w.kv_len = kv_len
+        try:
+            ehs = model._embed(w, hidden_states, encoder_hidden_states)
+            keep = {}
+            temb, st = model._temb(B, timestep.to(model.store.device), guidance, pooled_projections, keep=keep)
+            cos, sin = model._rope(txt_ids, img_ids)
+            mods = []
+            blk = 0
+            for i in range(cfg.num_layers):
+                tr.block_in[blk].copy_(w.X)
+                mods.append(model._double_block(i, w, st, cos, sin, keep=tr.keep[blk] if tr.keep else None))
+                blk += 1
+            for i in range(cfg.num_single_layers):
+                tr.block_in[blk].copy_(w.X)
+                mods.append(model._single_block(i, w, st, cos, sin, keep=tr.keep[blk] if tr.keep else None))
+                blk += 1
+            tr.x_final.copy_(w.X)
+            out, e = model._head(w, st)
+        finally:
+            w.kv_len = None
+        model.last_train_route = "plain" if kv_len is None else "padded_kv"
+        model.padded_kv_train_calls += int(kv_len is not None)
         # the saved activations live in the model's shared per-shape workspace: ONE pending backward per model at a time
         # (INTEGRATION.md).  A second grad-enabled forward before this one's backward would overwrite them: stamped here,
         # checked in backward.
         w.train.generation = getattr(w.train, "generation", 0) + 1
         ctx.generation = w.train.generation
         ctx.model, ctx.w, ctx.tr = model, w, tr
+        ctx.kv_len, ctx.rows = kv_len, N
         ctx.saved = dict(ehs=ehs, in16=w.in16.clone(), temb=temb, st=st, keep=keep, cos=cos, sin=sin, mods=mods, e=e)
-        return out
+        return out if kv_len is None else out[:, :N].contiguous()
 
     @staticmethod
     def backward(ctx, dout):
@@ -210,7 +225,18 @@ class FluxFunction(torch.autograd.Function):
             raise MgxError("FluxTransformer2DModel: the activations of this forward pass were overwritten by a later "
                            "grad-enabled forward of the same model (one pending backward per model; call backward() "
                            "before the next training forward)")
-        _backward(ctx.model, ctx.w, ctx.tr, ctx.saved, dout.contiguous().to(BF16))
+        dout = dout.contiguous().to(BF16)
+        if ctx.kv_len is None:
+            _backward(ctx.model, ctx.w, ctx.tr, ctx.saved, dout)
+            return (None,) * 9
+        # padded: the padding tokens' rows of dout are zero, and stay zero in every gradient behind them
+        pad = dout.new_zeros(dout.shape[0], ctx.w.N, dout.shape[2])
+        pad[:, :ctx.rows] = dout
+        ctx.w.kv_len = ctx.kv_len
+        try:
+            _backward(ctx.model, ctx.w, ctx.tr, ctx.saved, pad)
+        finally:
+            ctx.w.kv_len = None
         return (None,) * 9
 
 
@@ -262,6 +288,17 @@ def _dgrad_pair(model, tr, dC1: Rows, wname1, out1: Rows, dC2: Rows, wname2, out
         ops.transpose(Rows.of(W), K, Wt, N)
         Wts.append(Wt)
     ops.gemm_pair(dC1, Wts[0], None, out1, dC2, Wts[1], None, out2, K, N, epi, aux1=aux1, aux2=aux2, ldaux=ldaux)
+
+
+def _attn_bwd(w, Q, K, V, Qt, Kt, O, dO, lse, tr, B, H, S, Sp, ldo, o_bstride, scale):
+    """The attention backward of one block into tr.dQ / dK / dV.  On a padded workspace (w.kv_len set; every buffer allocated
+    at S % 256 == 0) the masked-tail pair: rows >= kv_len contribute nothing and their dQ / dK / dV rows come back zero."""
+    if w.kv_len is None:
+        ops.attn_bwd(Q, K, V, Qt, Kt, O, dO, lse, tr.delta, tr.dOt, tr.dQ, tr.dK, tr.dV, B, H, S, Sp, ldo, o_bstride, scale)
+    elif not ops.attn_bwd_kv(Q, K, V, Qt, Kt, O, dO, lse, tr.delta, tr.dOt, tr.dQ, tr.dK, tr.dV, B, H, S, w.kv_len, ldo, o_bstride,
+                             scale):
+        from ._lib import MgxError
+        raise MgxError(f"mgx_attn_bwd_kv refused B {B} H {H} Sa {S} kv_len {w.kv_len} after its path query took it")
 
 
 def _skinny_bwd(model, tr, dmod, x, wname, bname, N, K, dx_acc):
@@ -349,11 +386,9 @@ def _backward(model, w, tr, sv, dout):
         ops.gemm(dyr, Wt[d:5 * d], None, Rows(dbig[0, 3 * d:], M, 7 * d), 4 * d, d, EPI_DGELU, aux=save["hid_pre"],
                  ldaux=4 * d)
         if lean:
-            ops.attn_bwd(w.Q, w.K, save["V"], save["Qt"], save["Kt"], kept["O"], dO1, lse_b, tr.delta, tr.dOt, tr.dQ, tr.dK,
-                         tr.dV, B, H, S, Sp, d, S * d, scale)
+            _attn_bwd(w, w.Q, w.K, save["V"], save["Qt"], save["Kt"], kept["O"], dO1, lse_b, tr, B, H, S, Sp, d, S * d, scale)
         else:
-            ops.attn_bwd(w.Q, w.K, save["V"], save["Qt"], save["Kt"], w.cat, tr.dO, lse_b, tr.delta, tr.dOt, tr.dQ, tr.dK,
-                         tr.dV, B, H, S, Sp, 5 * d, S * 5 * d, scale)
+            _attn_bwd(w, w.Q, w.K, save["V"], save["Qt"], save["Kt"], w.cat, tr.dO, lse_b, tr, B, H, S, Sp, 5 * d, S * 5 * d, scale)
         # qk norm / rope backward writes [dq|dk|dv] straight into columns 0..3d of the [M, 7d] staging matrix
         qkv_b = kept["qkv"] if kept is not None and "qkv" in kept else w.qkv
         ops.qk_norm_rope_bwd(qkv_b, model.W32(f"{p}.attn.norm_q.weight"), model.W32(f"{p}.attn.norm_k.weight"), cos, sin,
@@ -417,8 +452,7 @@ def _backward(model, w, tr, sv, dout):
                    f"{p}.attn.{outn}.bias")
         _dgrad_pair(model, tr, Rows.of(tr.dy[sl["txt"]]), f"{p}.attn.to_add_out.weight", srows(dO3, "txt", d),
                     Rows.of(tr.dy[sl["img"]]), f"{p}.attn.to_out.0.weight", srows(dO3, "img", d), d, d)
-        ops.attn_bwd(w.Q, w.K, save["V"], save["Qt"], save["Kt"], O_b, dO3, lse_b, tr.delta, tr.dOt, tr.dQ, tr.dK, tr.dV,
-                     B, H, S, Sp, d, S * d, scale)
+        _attn_bwd(w, w.Q, w.K, save["V"], save["Qt"], save["Kt"], O_b, dO3, lse_b, tr, B, H, S, Sp, d, S * d, scale)
         qkv_b = kept["qkv"] if kept is not None and "qkv" in kept else w.qkv
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             ops.qk_norm_rope_bwd(qkv_b[sl[name]], model.W32(f"{p}.attn.{nq}.weight"), model.W32(f"{p}.attn.{nk}.weight"), cos,

@@ -235,9 +235,10 @@ def attn_fwd_path(B, H, S, Sp, ldo, o_bstride):
     return r
 
 
-# The no-grad forward pads a sequence that is off 256 to the next multiple and masks the padded keys (attn_fwd_log2_kv), so that
-# the 64-query attention and the fused projections apply (flux.py, _forward_nograd).  Off by default: the training replay
-# keeps the unpadded kernels (the backward has no masked tail), so rollout and replay would differ in their attention kernels.
+# A sequence that is off 256 is padded to the next multiple with the padding masked (attn_fwd_log2_kv, attn_bwd_kv), so that the
+# 64-wide attention kernels and the fused projections apply: the no-grad forward (flux.py, _forward_nograd) and the training
+# forward / recompute / backward (FluxFunction) alike, so rollout and replay of a sample run the same kernels on the same
+# padded shape.  Off by default.
 ATTN_PAD_KV = os.environ.get("MGX_ATTN_PAD_KV", "0") != "0"
 
 
@@ -344,6 +345,23 @@ def adamw_step(w, w16, g, m, v, lr, beta1, beta2, eps, wd, step, gnorm_sq, max_n
 def attn_bwd(Q, K, V, Qt, Kt, O, dO, lse, delta, dOt, dQ, dK, dV, B, H, S, Sp, ldo, o_bstride, scale):
     check(lib().mgx_attn_bwd(ptr(Q), ptr(K), ptr(V), ptr(Qt), ptr(Kt), O.data_ptr(), dO.data_ptr(), ptr(lse), ptr(delta),
                              ptr(dOt), ptr(dQ), ptr(dK), ptr(dV), B, H, S, Sp, ldo, o_bstride, scale, stream()))
+
+
+def attn_bwd_kv(Q, K, V, Qt, Kt, O, dO, lse, delta, dOt, dQ, dK, dV, B, H, Sa, kv_len, ldo, o_bstride, scale):
+    """attn_bwd on operands allocated at Sa (% 256 == 0) with the keys and queries >= kv_len masked and the rows >= kv_len of
+    dQ / dK / dV written as zero (`mgx_attn_bwd_kv`).  False -- nothing launched -- when the 64-wide pair cannot take the
+    problem (attn_bwd_kv_path): there is no other kernel behind it."""
+    rc = lib().mgx_attn_bwd_kv(ptr(Q), ptr(K), ptr(V), ptr(Qt), ptr(Kt), O.data_ptr(), dO.data_ptr(), ptr(lse), ptr(delta),
+                               ptr(dOt), ptr(dQ), ptr(dK), ptr(dV), B, H, Sa, kv_len, ldo, o_bstride, scale, stream())
+    if rc == 1:
+        return False
+    check(rc)
+    return True
+
+
+def attn_bwd_kv_path(B, H, Sa, kv_len, ldo, o_bstride):
+    """1 when attn_bwd_kv takes this problem, 0 when it refuses it.  Launches nothing."""
+    return lib().mgx_attn_bwd_kv_path(B, H, Sa, kv_len, ldo, o_bstride)
 
 
 # ------------------------------------------------------------------------------------------------ VAE decode (csrc/vae.hip)
