@@ -331,6 +331,14 @@ int mgx_attn_bwd_kv(const uint16_t* Q, const uint16_t* K, const uint16_t* V, con
                     void* stream);
 int mgx_attn_bwd_kv_path(int B, int H, int Sa, int kv_len, long ldo, long o_bstride);
 
+/* The launch operands that the masked 64-wide kernels derive from kv_len (csrc/attn_operands.h, the one derivation the
+ * kernels call), for the CPU tests that hold them equal to the generators' kv_operands.  stream: 0 = mgx_attn_fwd_log2_kv
+ * (nloop, kmax, vmax, kt, kvm1), 1 = dQ (nloop, seq, kt0, kt1, qlast), 2 = dK / dV (nloop, qmax, cmax, qk, klast), the last two
+ * of mgx_attn_bwd_kv; block = the workgroup's 256-row block (streams 1 and 2).  Writes the values to out[0 .. cap) in that
+ * order and returns their count (5); MGX_ERR_ARG for another stream, kv_len < 1, a null out or cap too small.  Host code
+ * only: needs no GPU. */
+int mgx_attn_kv_operands(int stream, int kv_len, int block, int* out, int cap);
+
 /* out[b, :] = bf16(x[b, :] @ W[N,K]^T + bias), 1 <= Bn <= 16 rows (temb MLPs, AdaLN modulation linears) */
 int mgx_skinny_linear(const uint16_t* x, long ldx, const uint16_t* W, long ldw, const uint16_t* bias, uint16_t* out,
                       long ldo, int Bn, int N, int K, void* stream);

@@ -82,6 +82,7 @@ SIGNATURES = {
     "mgx_attn_bwd": (_I, [_P] * 13 + [_I] * 4 + [_L, _L, _F, _P]),
     "mgx_attn_bwd_kv": (_I, [_P] * 13 + [_I] * 4 + [_L, _L, _F, _P]),
     "mgx_attn_bwd_kv_path": (_I, [_I] * 4 + [_L, _L]),
+    "mgx_attn_kv_operands": (_I, [_I] * 3 + [C.POINTER(_I), _I]),
     "mgx_skinny_linear": (_I, [_P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _P]),
     "mgx_skinny_wgrad": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _P]),
     "mgx_skinny_dgrad_workspace": (_L, [_I, _I]),

@@ -14,6 +14,7 @@
 // round trip); Vt is stored in LDS in the matching permuted key order, so both the K and the Vt fragments are single,
 // bank-conflict-free ds_read_b128 (XOR-swizzled images).
 #include "../../include/mixgrpo_hip.h"
+#include "attn_operands.h"
 #include "common.h"
 
 #include <cstdlib>
@@ -49,36 +50,19 @@ __device__ __forceinline__ int k_off(int key, int chunk) { return key * 256 + ((
 // the LDS-active cycles and the LDS port, not the matrix pipe, paced the kernel.)  slot ^= (d >> 1) & 7.
 __device__ __forceinline__ int v_off(int d, int slot16) { return d * 128 + ((slot16 ^ ((d >> 1) & 7)) << 4); }
 
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  const f32x2_t v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));   // one v_cvt_pk_bf16_f32
-}
-
-// NW waves per workgroup (QB = 32*NW queries).  NW = 4 puts two independent workgroups on a CU (64 KiB LDS each): their
-// barriers are unrelated, so one workgroup's softmax VALU phase runs under the other's MFMA phase instead of the two
-// waves of a SIMD marching in lockstep.
-// OVL: the P V product of the tile's first 32 keys (8 MFMAs) is issued BESIDE the exponentials of its last 32 keys, inside
-// one scheduling region with `sched_group_barrier` hints (1 MFMA : 2 v_exp : 5 other VALU per gap -- 36 issue cycles per
-// 32-cycle MFMA).  In-kernel stamps showed the softmax VALU phase (1100-1600 cycles per wave and tile) and the MFMA phases
-// (2 x ~600) adding up almost serially: both waves of a SIMD are in the same phase at the same time.
-template <int NW, bool DEFER, bool OVL = false>
-__global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
-  constexpr int QB = QW * NW;
-  constexpr int NCH = 1024 / (NW * 64);   // 16-byte chunks per thread per operand tile
+// The P V product of the tile's first 32 keys (8 MFMAs) is issued BESIDE the exponentials of its last 32 keys, inside one
+// scheduling region with `sched_group_barrier` hints (1 MFMA : 2 v_exp : 5 other VALU per gap -- 36 issue cycles per 32-cycle
+// MFMA).  In-kernel stamps showed the softmax VALU phase (1100-1600 cycles per wave and tile) and the MFMA phases (2 x ~600)
+// adding up almost serially: both waves of a SIMD are in the same phase at the same time.
+__global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs g) {
+  constexpr int QB = QW * 8;               // 8 waves: 256 queries per workgroup
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][K tile | Vt tile]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
 
   const int nq = (g.S + QB - 1) / QB;
-  // XCD-aware order: the q-tiles of one (b, head) stay on one XCD so its K/V stay in that L2
-  const int nwg = nq * g.H * g.B;
   int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-  }
+  xcd_remap(bid, nq * g.H * g.B);
   const int qt = bid % nq;
   const int bh = bid / nq;
   const int b = bh / g.H, hh = bh - b * g.H;
@@ -96,14 +80,14 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
   for (int ks = 0; ks < 8; ++ks)
     qf[ks] = *reinterpret_cast<const s16x8*>(Qp + (long)qrow * HD + ks * 16 + h * 8);
 
-  // ---- staging: K tile = 1024 16-B chunks, Vt tile = 1024 16-B chunks; NCH of each per thread
-  const int kc_key0 = tid >> 4, kc_chunk = tid & 15;          // chunk id = tid + NW*64*i: key = id>>4
-  const int vc_d0 = tid >> 3, vc_chunk = tid & 7;             // chunk id = tid + NW*64*i: d = id>>3, 16-B chunk of 64 keys
-  constexpr int KSTEP = NW * 4, DSTEP = NW * 8;               // keys / d rows advanced per pass
-  uint4 sk0, sk1, sk2, sk3, sv0, sv1, sv2, sv3;   // named (not an array): keeps the staging registers out of scratch
+  // ---- staging: K tile = 1024 16-B chunks, Vt tile = 1024 16-B chunks; two of each per thread
+  const int kc_key0 = tid >> 4, kc_chunk = tid & 15;          // chunk id = tid + 512*i: key = id>>4
+  const int vc_d0 = tid >> 3, vc_chunk = tid & 7;             // chunk id = tid + 512*i: d = id>>3, 16-B chunk of 64 keys
+  constexpr int KSTEP = 32, DSTEP = 64;                       // keys / d rows advanced per pass
+  uint4 sk0, sk1, sv0, sv1;   // named (not an array): keeps the staging registers out of scratch
   const int ntiles = (g.S + KB - 1) / KB;
 #define LOAD1(i_, SK, SV)                                                                           \
-  if constexpr (NCH > i_) {                                                                         \
+  {                                                                                                 \
     int ka = key_base + kc_key0 + KSTEP * i_;                                                       \
     if (ka >= g.S) ka = g.S - 1;                                                                    \
     SK = *reinterpret_cast<const uint4*>(Kp + (long)ka * HD + kc_chunk * 8);                        \
@@ -112,10 +96,10 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
 #define LOAD_KV(t)                                                                                  \
   do {                                                                                              \
     const int key_base = (t) * KB;                                                                  \
-    LOAD1(0, sk0, sv0) LOAD1(1, sk1, sv1) LOAD1(2, sk2, sv2) LOAD1(3, sk3, sv3)                     \
+    LOAD1(0, sk0, sv0) LOAD1(1, sk1, sv1)                                                           \
   } while (0)
 #define STORE1(i_, SK, SV)                                                                          \
-  if constexpr (NCH > i_) {                                                                         \
+  {                                                                                                 \
     *reinterpret_cast<uint4*>(kb_ptr + k_off(kc_key0 + KSTEP * i_, kc_chunk)) = SK;                 \
     /* 16-byte chunk vc_chunk = keys 8c..8c+7 of the tile: 4-key groups g = 2c, 2c+1 of block b = c >> 1 */ \
     *reinterpret_cast<uint2*>(vb_ptr + v_off(vc_d0 + DSTEP * i_, (vc_chunk >> 1) * 2) + (vc_chunk & 1) * 8) = make_uint2(SV.x, SV.y); \
@@ -125,7 +109,7 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
   do {                                                                                              \
     char* kb_ptr = smem + (buf) * (K_TILE_BYTES + V_TILE_BYTES);                                    \
     char* vb_ptr = kb_ptr + K_TILE_BYTES;                                                           \
-    STORE1(0, sk0, sv0) STORE1(1, sk1, sv1) STORE1(2, sk2, sv2) STORE1(3, sk3, sv3)                 \
+    STORE1(0, sk0, sv0) STORE1(1, sk1, sv1)                                                         \
   } while (0)
 
   f32x16 o[4];   // O^T tiles: d in [32*dt, 32*dt+32), column = query r
@@ -146,11 +130,9 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
   int cur = 0;
   // one K/V tile: S^T, online softmax, O^T accumulation.  Kept as a lambda over a compile-time MASK so the full
   // tiles carry no masking selects (hipcc if-converts a runtime "last tile" test into ~200 v_cndmask per tile).
-#define STAMP(k_) do {} while (0)
   auto tile = [&](int t, auto mask_tag) __attribute__((always_inline)) {
     constexpr bool MASK = decltype(mask_tag)::value;
     if (t + 1 < ntiles) LOAD_KV(t + 1);
-    STAMP(0);
     const char* ks_ = smem + cur * (K_TILE_BYTES + V_TILE_BYTES);
     const char* vs_ = ks_ + K_TILE_BYTES;
 
@@ -177,7 +159,6 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) s[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], s[1], 0, 0, 0);
     }
-    STAMP(1);
     // first Vt fragments of the P V product: requested here so that they return underneath the softmax
     s16x8 vfr[2][4];
 #pragma unroll
@@ -201,15 +182,14 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) mx = fmaxf(mx, s[kb][i]);
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // Deferred rescale (DEFER): the running maximum is only raised -- and O, l rescaled -- when some row of the wave
+    // Deferred rescale: the running maximum is only raised -- and O, l rescaled -- when some row of the wave
     // has outgrown it by more than 2^DEFER_LOG2; otherwise the stale maximum is kept and this tile's P may reach
     // 2^DEFER_LOG2 instead of 1 (fp32 row sums and accumulators, bf16 P: the relative precision is unchanged).  The
     // decision is taken BEFORE this tile's P is exponentiated and after the previous tile's P V has been issued, so
     // everything still at the old scale (O, l) is rescaled exactly once and nothing at the new scale is.  It saves the
     // 64 v_mul of the O rescale (a quarter of the tile's VALU work) on almost every tile.
     constexpr float DEFER_LOG2 = 6.0f;
-    bool rescale = true;
-    if (DEFER) rescale = __builtin_amdgcn_ballot_w64((mx - m_run) * g.scale_log2e > DEFER_LOG2) != 0;   // -inf run max: true
+    const bool rescale = __builtin_amdgcn_ballot_w64((mx - m_run) * g.scale_log2e > DEFER_LOG2) != 0;   // -inf run max: true
     float alpha = 1.0f;
     if (rescale) {
       const float m_new = fmaxf(m_run, mx);
@@ -236,56 +216,32 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
       const int kb = idx >> 1, s2 = idx & 1;
       return __builtin_bit_cast(s16x8, make_uint4(pb[kb][4 * s2], pb[kb][4 * s2 + 1], pb[kb][4 * s2 + 2], pb[kb][4 * s2 + 3]));
     };
-    if constexpr (OVL) {
-      exps(0);
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) vfr[1][dt] = *reinterpret_cast<const s16x8*>(vs_ + v_off(dt * 32 + r, 2 + h));
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- one scheduling region: 8 MFMAs (keys 0..31) + the exponentials of keys 32..63 + the V fragments of idx 2
-      {
-        const s16x8 pf0 = pfrag(0), pf1 = pfrag(1);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[0][dt], pf0, o[dt], 0, 0, 0);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) vfr[0][dt] = *reinterpret_cast<const s16x8*>(vs_ + v_off(dt * 32 + r, 4 + h));
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[1][dt], pf1, o[dt], 0, 0, 0);
-        exps(1);
-#pragma unroll
-        for (int k_ = 0; k_ < 8; ++k_) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // 1 MFMA
-          __builtin_amdgcn_sched_group_barrier(0x400, 2, 0);     // 2 transcendental (v_exp_f32)
-          __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);     // 5 other VALU
-          if (k_ == 3) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);   // the four V fragment reads of idx 2
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      l_run = l_run * alpha + psum;
-      STAMP(2);
-#pragma unroll
-      for (int idx = 2; idx < 4; ++idx) {
-        const s16x8 pf = pfrag(idx);
-        if (idx + 1 < 4) {
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt)
-            vfr[(idx + 1) & 1][dt] = *reinterpret_cast<const s16x8*>(vs_ + v_off(dt * 32 + r, (idx + 1) * 2 + h));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[idx & 1][dt], pf, o[dt], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
     exps(0);
-    exps(1);
-    l_run = l_run * alpha + psum;
-    STAMP(2);
-
-    // ---- O^T += Vt P^T : A = Vt[d = 32*dt + r][slot (b = 2 kb + s2, h)]: the 8 keys of lane half h in the S^T
-    // accumulator's order; the four fragments of step idx + 1 are requested before the MFMAs of step idx
 #pragma unroll
-    for (int idx = 0; idx < 4; ++idx) {
+    for (int dt = 0; dt < 4; ++dt) vfr[1][dt] = *reinterpret_cast<const s16x8*>(vs_ + v_off(dt * 32 + r, 2 + h));
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- one scheduling region: 8 MFMAs (keys 0..31) + the exponentials of keys 32..63 + the V fragments of idx 2
+    {
+      const s16x8 pf0 = pfrag(0), pf1 = pfrag(1);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[0][dt], pf0, o[dt], 0, 0, 0);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) vfr[0][dt] = *reinterpret_cast<const s16x8*>(vs_ + v_off(dt * 32 + r, 4 + h));
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[1][dt], pf1, o[dt], 0, 0, 0);
+      exps(1);
+#pragma unroll
+      for (int k_ = 0; k_ < 8; ++k_) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // 1 MFMA
+        __builtin_amdgcn_sched_group_barrier(0x400, 2, 0);     // 2 transcendental (v_exp_f32)
+        __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);     // 5 other VALU
+        if (k_ == 3) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);   // the four V fragment reads of idx 2
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    l_run = l_run * alpha + psum;
+#pragma unroll
+    for (int idx = 2; idx < 4; ++idx) {
       const s16x8 pf = pfrag(idx);
       if (idx + 1 < 4) {
 #pragma unroll
@@ -298,19 +254,14 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
         o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr[idx & 1][dt], pf, o[dt], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    }
-    STAMP(3);
     if (t + 1 < ntiles) STORE_KV(cur ^ 1);
-    STAMP(4);
     __syncthreads();
-    STAMP(5);
     cur ^= 1;
   };
   const int nfull = g.S / KB;
   for (int t = 0; t < nfull; ++t) tile(t, std::false_type{});
   if (nfull < ntiles) tile(nfull, std::true_type{});
 
-#undef STAMP
   // ---- finalize: row sum across the two half-waves, normalise, store O[q][h*128 + d]
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_tot;
@@ -355,13 +306,13 @@ __global__ void __launch_bounds__(NW * 64, 2) attn_fwd_kernel(AttnArgs g) {
                  [k_hi] "s"((unsigned)(kp >> 32)), [v_lo] "s"((unsigned)vp), [v_hi] "s"((unsigned)(vp >> 32)), \
                  [o_lo] "s"((unsigned)op), [o_hi] "s"((unsigned)(op >> 32)), [l_lo] "s"((unsigned)lp), \
                  [l_hi] "s"((unsigned)(lp >> 32)), [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)), [cs] "s"(g.scale_log2e), \
-                 [nloop] "s"(nloop), [kmax] "s"((ntiles - 1) * 16384), [vmax] "s"((ntiles - 1) * 128), \
+                 [nloop] "s"(ops.nloop), [kmax] "s"(ops.kmax), [vmax] "s"(ops.vmax), \
                  [nblk] "s"(count), [qt0] "s"(qt), [hh0] "s"(hh), [b0] "s"(b), [nq] "s"(nq), [nh] "s"(g.H), [kstep] "s"(g.S * 256), \
                  [ostep] "s"(ostep), [obs] "s"((int)(g.o_bstride * 2)), [ob_lo] "s"((unsigned)ob), [ob_hi] "s"((unsigned)(ob >> 32)), \
                  [sq] "s"(stride % nq), [dbh] "s"(stride / nq), [qstride] "s"(stride * 65536), [lstride] "s"(stride * 1024)
-// KV: four bytes, 8 + the number of valid keys (0 .. 64) of the first tile and of the last three (gen/attn_fwd64.py, mask_key)
+// (readfirstlane: the clamp is selected as a vector med3, and an "s" operand has to be in a scalar register)
 #define ATTN_FWD64_KV_OPERANDS \
-  ATTN_FWD64_OPERANDS, [kt] "s"(kt), [kvm1] "s"(g.kv_len - 1)
+  ATTN_FWD64_OPERANDS, [kt] "s"(__builtin_amdgcn_readfirstlane(ops.kt)), [kvm1] "s"(ops.kvm1)
 
 template <bool ACC, bool KV = false>
 __global__ void __launch_bounds__(256, 1) attn_fwd64_kernel(AttnArgs g) {
@@ -394,15 +345,8 @@ __global__ void __launch_bounds__(256, 1) attn_fwd64_kernel(AttnArgs g) {
   const unsigned long long ob = (unsigned long long)g.O;
   const unsigned long long op = (unsigned long long)(g.O + (long)b * g.o_bstride + (long)(qt * 256) * g.ldo + hh * HD);
   const unsigned long long lp = g.lse ? (unsigned long long)(g.lse + (long)bh * g.S + qt * 256) : 0ull;
-  // K / V^T tiles walked.  KV: those with a valid key, rounded up to a pair (the loop is unrolled by two), at least four
-  // (first tile, one peeled pair, last tile: at S = 256 nothing is dropped and up to all four tiles are partial)
-  const int ntiles = KV ? max(4, (((g.kv_len + 63) >> 6) + 1) & ~1) : g.S >> 6;
-  const int nloop = KV ? (ntiles - 4) >> 1 : (ntiles - 2) >> 1;
-  const int ostep = (int)(g.ldo * 512);                       // bytes of 256 rows of O
-  auto kv_tile = [&](int t) { return 8 + min(64, max(0, g.kv_len - 64 * t)); };
-  // (readfirstlane: the clamp is selected as a vector med3, and an "s" operand has to be in a scalar register)
-  [[maybe_unused]] const int kt = __builtin_amdgcn_readfirstlane(kv_tile(0) | kv_tile(ntiles - 3) << 8 | kv_tile(ntiles - 2) << 16 |
-                                                                 kv_tile(ntiles - 1) << 24);
+  const attn_ops::Fwd64 ops = attn_ops::fwd64(KV, g.S, g.kv_len);   // the K / V^T tiles walked, the masked tail's counts
+  const int ostep = (int)(g.ldo * 512);                            // bytes of 256 rows of O
   if constexpr (KV) asm volatile(ATTN_FWD64QK_BODY : : ATTN_FWD64_KV_OPERANDS : ATTN_FWD64QK_CLOBBERS);
   else if constexpr (ACC) asm volatile(ATTN_FWD64Q_BODY : : ATTN_FWD64_OPERANDS : ATTN_FWD64Q_CLOBBERS);
   else asm volatile(ATTN_FWD64_BODY : : ATTN_FWD64_OPERANDS : ATTN_FWD64_CLOBBERS);
@@ -427,40 +371,29 @@ static bool attn_fwd_wide(int B, int H, int S, int Sp, long ldo, long o_bstride,
          (long)S * 256 < (1L << 31);
 }
 
+static AttnArgs attn_fwd_args(const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, uint16_t* O, float* lse, int B, int H,
+                              int S, int Sp, int kv_len, long ldo, long o_bstride, float scale_log2e) {
+  AttnArgs g;
+  g.Q = Q; g.K = K; g.Vt = Vt; g.O = O; g.lse = lse;
+  g.B = B; g.H = H; g.S = S; g.Sp = Sp; g.ldo = ldo; g.o_bstride = o_bstride;
+  g.scale_log2e = scale_log2e;
+  g.kv_len = kv_len;
+  return g;
+}
+
 static int attn_fwd_any(const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, uint16_t* O, float* lse, int B, int H, int S,
                         int Sp, long ldo, long o_bstride, float scale_log2e, bool log2_scores, void* stream) {
   MGX_REQUIRE(Q && K && Vt && O, "null operand");
   MGX_REQUIRE(B > 0 && H > 0 && S > 0, "empty attention");
   MGX_REQUIRE(Sp >= S && Sp % 64 == 0, "Sp must be S rounded up to a multiple of 64");
   MGX_REQUIRE(ldo % 4 == 0 && o_bstride % 4 == 0, "output strides must keep 8-byte alignment");
-  AttnArgs g;
-  g.Q = Q; g.K = K; g.Vt = Vt; g.O = O; g.lse = lse;
-  g.B = B; g.H = H; g.S = S; g.Sp = Sp; g.ldo = ldo; g.o_bstride = o_bstride;
-  g.scale_log2e = scale_log2e;
-  g.kv_len = S;
-  static const int nw = getenv("MGX_ATTN_NW") ? atoi(getenv("MGX_ATTN_NW")) : 8;
-  static const int defer = getenv("MGX_ATTN_DEFER") ? atoi(getenv("MGX_ATTN_DEFER")) : 1;
-  const int lds = 2 * (K_TILE_BYTES + V_TILE_BYTES);
+  const AttnArgs g = attn_fwd_args(Q, K, Vt, O, lse, B, H, S, Sp, S, ldo, o_bstride, scale_log2e);
   hipStream_t st = (hipStream_t)stream;
-  static const int ovl = getenv("MGX_ATTN_OVL") ? atoi(getenv("MGX_ATTN_OVL")) : 1;
   int grid64 = 0;
-  if (attn_fwd_wide(B, H, S, Sp, ldo, o_bstride, &grid64)) {
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)attn_fwd64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-      (void)hipFuncSetAttribute((const void*)attn_fwd64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-      attr = true;
-    }
-    if (log2_scores) attn_fwd64_kernel<true><<<grid64, 256, 65536, st>>>(g);
-    else attn_fwd64_kernel<false><<<grid64, 256, 65536, st>>>(g);
-    MGX_CHECK_LAUNCH();
-    return MGX_OK;
-  }
-  if (nw == 8 && defer && ovl) attn_fwd_kernel<8, true, true><<<cdiv(S, 256) * H * B, 512, lds, st>>>(g);
-  else if (nw == 8 && defer) attn_fwd_kernel<8, true><<<cdiv(S, 256) * H * B, 512, lds, st>>>(g);
-  else if (nw == 8) attn_fwd_kernel<8, false><<<cdiv(S, 256) * H * B, 512, lds, st>>>(g);
-  else if (defer) attn_fwd_kernel<4, true><<<cdiv(S, 128) * H * B, 256, lds, st>>>(g);
-  else attn_fwd_kernel<4, false><<<cdiv(S, 128) * H * B, 256, lds, st>>>(g);
+  if (!attn_fwd_wide(B, H, S, Sp, ldo, o_bstride, &grid64))
+    attn_fwd_kernel<<<cdiv(S, 256) * H * B, 512, 2 * (K_TILE_BYTES + V_TILE_BYTES), st>>>(g);
+  else if (log2_scores) launch_lds<attn_fwd64_kernel<true>, 65536>(grid64, 256, st, g);
+  else launch_lds<attn_fwd64_kernel<false>, 65536>(grid64, 256, st, g);
   MGX_CHECK_LAUNCH();
   return MGX_OK;
 }
@@ -488,17 +421,8 @@ extern "C" int mgx_attn_fwd_log2_kv(const uint16_t* Q2, const uint16_t* K, const
   MGX_REQUIRE(ldo % 4 == 0 && o_bstride % 4 == 0, "output strides must keep 8-byte alignment");
   int grid64 = 0;
   if (!attn_fwd_kv_wide(B, H, Sa, kv_len, ldo, o_bstride, &grid64)) return 1;   // nothing launched: the caller's unpadded path
-  AttnArgs g;
-  g.Q = Q2; g.K = K; g.Vt = Vt; g.O = O; g.lse = lse;
-  g.B = B; g.H = H; g.S = Sa; g.Sp = Sa; g.ldo = ldo; g.o_bstride = o_bstride;
-  g.scale_log2e = 1.0f;
-  g.kv_len = kv_len;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd64_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    attr = true;
-  }
-  attn_fwd64_kernel<true, true><<<grid64, 256, 65536, (hipStream_t)stream>>>(g);
+  launch_lds<attn_fwd64_kernel<true, true>, 65536>(
+      grid64, 256, (hipStream_t)stream, attn_fwd_args(Q2, K, Vt, O, lse, B, H, Sa, Sa, kv_len, ldo, o_bstride, 1.0f));
   MGX_CHECK_LAUNCH();
   return MGX_OK;
 }
@@ -511,4 +435,22 @@ extern "C" int mgx_attn_fwd_path(int B, int H, int S, int Sp, long ldo, long o_b
   MGX_REQUIRE(B > 0 && H > 0 && S > 0, "empty attention");
   MGX_REQUIRE(Sp >= S && Sp % 64 == 0, "Sp must be S rounded up to a multiple of 64");
   return attn_fwd_wide(B, H, S, Sp, ldo, o_bstride, nullptr) ? 1 : 0;
+}
+
+// The launch operands of the masked 64-wide streams as the kernels derive them (attn_operands.h), for the CPU tests that hold
+// them equal to the generators' kv_operands: stream 0 = forward (nloop, kmax, vmax, kt, kvm1), 1 = dQ (nloop, seq, kt0, kt1,
+// qlast), 2 = dK / dV (nloop, qmax, cmax, qk, klast); `block` = the 256-row block of the workgroup (streams 1 and 2).
+extern "C" int mgx_attn_kv_operands(int stream, int kv_len, int block, int* out, int cap) {
+  MGX_REQUIRE(stream >= 0 && stream <= 2 && kv_len >= 1 && out && cap >= 5, "bad stream, kv_len or output capacity");
+  if (stream == 0) {
+    const attn_ops::Fwd64 o = attn_ops::fwd64(true, 0, kv_len);
+    out[0] = o.nloop; out[1] = o.kmax; out[2] = o.vmax; out[3] = o.kt; out[4] = o.kvm1;
+  } else if (stream == 1) {
+    const attn_ops::Dq64 o = attn_ops::dq64(true, 0, kv_len, block);
+    out[0] = o.nloop; out[1] = o.seq; out[2] = o.kt0; out[3] = o.kt1; out[4] = o.qlast;
+  } else {
+    const attn_ops::Dkv64 o = attn_ops::dkv64(true, 0, kv_len, block);
+    out[0] = o.nloop; out[1] = o.qmax; out[2] = o.cmax; out[3] = o.qk; out[4] = o.klast;
+  }
+  return 5;
 }

@@ -11,6 +11,7 @@
 // global memory ([B,H,128,Sp]: Qt, Kt by qk_norm_rope, dOt by attn_bwd_prep), so every LDS fragment read is a
 // plain conflict-free ds_read (XOR-swizzled images), cf. the forward kernel.
 #include "../../include/mixgrpo_hip.h"
+#include "attn_operands.h"
 #include "common.h"
 
 #include <cstdlib>
@@ -20,12 +21,6 @@ namespace {
 
 constexpr int HD = 128;
 
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  const f32x2_t v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));   // one v_cvt_pk_bf16_f32
-}
 // row-major [rows][128] bf16 image, 16-byte chunk swizzle
 __device__ __forceinline__ int rm_off(int row, int chunk) { return row * 256 + ((chunk ^ (row & 15)) << 4); }
 // Transposed images [128 d][64 or 32 columns] in 16-byte SLOTS: slot (b, h) of a row holds, for the 16-column block b,
@@ -56,16 +51,14 @@ __device__ __forceinline__ float buf_ld_f32(R rs, unsigned voff, unsigned soff) 
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, (int)soff, 0));
 }
 
-__device__ __forceinline__ void xcd_remap(int& bid, int nwg) {
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-}
-
 // ------------------------------------------------------------------------------------------------ prep
 // delta[b,h,s] = sum_d dO[b,s,h*128+d] * O[b,s,h*128+d];  dOt[b,h,d,s] = dO[b,s,h*128+d]
+// O and dO are read in the rows < valid only; delta [B,H,S] is written in the rows < S and dOt [B,H,128,Sp] in the columns
+// < Sp, zero from `valid` on.  mgx_attn_bwd: valid = S (rows S .. Sp of dOt are its zero padding); mgx_attn_bwd_kv: everything
+// is allocated at S = Sp = Sa, valid = kv_len, and what the padding rows of O and dO hold does not matter.
 __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(const bf16_raw* __restrict__ O, const bf16_raw* __restrict__ dO,
                                                             long ldo, long o_bstride, float* __restrict__ delta,
-                                                            bf16_raw* __restrict__ dOt, int H, int S, int Sp) {
+                                                            bf16_raw* __restrict__ dOt, int H, int S, int Sp, int valid) {
   __shared__ bf16_raw tile[64][130];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int hh = blockIdx.y, b = blockIdx.z, t0 = blockIdx.x * 64;
@@ -73,7 +66,7 @@ __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(const bf16_raw* __re
     const int tl = w * 16 + i, s = t0 + tl;
     uint32_t ud = 0;
     float acc = 0.f;
-    if (s < S) {
+    if (s < valid) {
       const long off = (long)b * o_bstride + (long)s * ldo + hh * HD + 2 * lane;
       ud = *reinterpret_cast<const uint32_t*>(dO + off);
       const uint32_t uo = *reinterpret_cast<const uint32_t*>(O + off);
@@ -93,43 +86,8 @@ __global__ void __launch_bounds__(256) attn_bwd_prep_kernel(const bf16_raw* __re
       u.y = (uint32_t)tile[c * 8 + 2][d] | ((uint32_t)tile[c * 8 + 3][d] << 16);
       u.z = (uint32_t)tile[c * 8 + 4][d] | ((uint32_t)tile[c * 8 + 5][d] << 16);
       u.w = (uint32_t)tile[c * 8 + 6][d] | ((uint32_t)tile[c * 8 + 7][d] << 16);
-      *reinterpret_cast<uint4*>(dst) = u;   // rows beyond S hold zeros (ud = 0)
+      *reinterpret_cast<uint4*>(dst) = u;   // columns from `valid` on hold zeros (ud = 0)
     }
-  }
-}
-
-// The kv_len form (mgx_attn_bwd_kv): everything is allocated at Sa rows / columns, rows >= kv_len are padding.  delta and dOt
-// of the rows < kv_len are the kernel's above bit for bit (the same loads, products and wave_sum); those >= kv_len are
-// written as zero whatever the padding rows of O and dO hold (they are not read).
-__global__ void __launch_bounds__(256) attn_bwd_prep_kv_kernel(const bf16_raw* __restrict__ O, const bf16_raw* __restrict__ dO,
-                                                               long ldo, long o_bstride, float* __restrict__ delta,
-                                                               bf16_raw* __restrict__ dOt, int H, int Sa, int kv_len) {
-  __shared__ bf16_raw tile[64][130];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int hh = blockIdx.y, b = blockIdx.z, t0 = blockIdx.x * 64;
-  for (int i = 0; i < 16; ++i) {
-    const int tl = w * 16 + i, s = t0 + tl;            // s < Sa: Sa % 64 == 0
-    uint32_t ud = 0;
-    float acc = 0.f;
-    if (s < kv_len) {
-      const long off = (long)b * o_bstride + (long)s * ldo + hh * HD + 2 * lane;
-      ud = *reinterpret_cast<const uint32_t*>(dO + off);
-      const uint32_t uo = *reinterpret_cast<const uint32_t*>(O + off);
-      acc = bf2f(ud & 0xffff) * bf2f(uo & 0xffff) + bf2f(ud >> 16) * bf2f(uo >> 16);
-    }
-    *reinterpret_cast<uint32_t*>(&tile[tl][2 * lane]) = ud;
-    acc = wave_sum(acc);
-    if (lane == 0) delta[((long)b * H + hh) * Sa + s] = acc;
-  }
-  __syncthreads();
-  for (int id = threadIdx.x; id < 128 * 8; id += 256) {
-    const int d = id >> 3, c = id & 7;
-    uint4 u;
-    u.x = (uint32_t)tile[c * 8 + 0][d] | ((uint32_t)tile[c * 8 + 1][d] << 16);
-    u.y = (uint32_t)tile[c * 8 + 2][d] | ((uint32_t)tile[c * 8 + 3][d] << 16);
-    u.z = (uint32_t)tile[c * 8 + 4][d] | ((uint32_t)tile[c * 8 + 5][d] << 16);
-    u.w = (uint32_t)tile[c * 8 + 6][d] | ((uint32_t)tile[c * 8 + 7][d] << 16);
-    *reinterpret_cast<uint4*>(dOt + (((long)b * H + hh) * HD + d) * Sa + t0 + c * 8) = u;
   }
 }
 
@@ -149,6 +107,7 @@ struct BwdArgs {
   int B, H, S, Sp;
   long ldo, o_bstride;
   float scale, scale_log2e, neg_inv_scale;
+  int kv_len;           // attn_bwd_*64_kernel<true> only: rows >= kv_len are padding (S = Sp is the allocated length Sa there)
 };
 
 // ------------------------------------------------------------------------------------------------ dK, dV
@@ -254,10 +213,8 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dkv_kernel(BwdArgs g) {
 #pragma unroll
   for (int ks = 0; ks < 8; ++ks) asm volatile("" :: "v"(kf[ks]));
   int cur = 0;
-#define STAMP(k_) do {} while (0)
   auto tile = [&](int t, auto mask_tag) __attribute__((always_inline)) {
     constexpr bool MASK = decltype(mask_tag)::value;
-    STAMP(0);
     const char* base = smem + cur * DKV_STAGE;
     const float* nls = reinterpret_cast<const float*>(base + 32768);     // -lse / scale per query row of the tile
     const float* ndl = nls + 32;                                         // -delta
@@ -293,7 +250,6 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dkv_kernel(BwdArgs g) {
     // S / dP phase, the register peak of the kernel (one K fragment was spilled into the loop); Q / dO tiles are L2 hits
     // (every key block of the (batch, head) reads them) and have the exp and dV / dK phases to land
     if (t + 1 < nqt) DKV_LOAD(t + 1);
-    STAMP(1);
     // P[q][key] and dS[q][key]; q = (i&3) + 8*(i>>2) + 4h (rows), key = this lane's column
     uint32_t pb[8], dsb[8];
 #pragma unroll
@@ -306,7 +262,6 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dkv_kernel(BwdArgs g) {
       pb[i >> 1] = pack_bf16(p0, p1);
       dsb[i >> 1] = pack_bf16(d0, d1);
     }
-    STAMP(2);
     // dV^T += dO^T P, dK^T += Q^T dS: 16 MFMAs, each with ONE operand from LDS (dOt / Qt images).  The reads run two
     // MFMAs ahead through a ring of three fragment registers (same reason as above: "read; mfma" pairs serialise into
     // read -> lgkmcnt(0) -> MFMA, one exposed LDS round trip per MFMA).
@@ -334,11 +289,8 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dkv_kernel(BwdArgs g) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    STAMP(3);
     if (t + 1 < nqt) { const int nt_ = t + 1; DKV_STORE(cur ^ 1); }
-    STAMP(4);
     __syncthreads();
-    STAMP(5);
     cur ^= 1;
   };
   if (key0 + 32 > g.S) {          // wave-uniform: only the ragged last key block carries the per-key mask
@@ -346,7 +298,6 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dkv_kernel(BwdArgs g) {
   } else {
     for (int t = 0; t < nqt; ++t) tile(t, std::false_type{});
   }
-#undef STAMP
   const int key = key0 + r;
   if (key < g.S) {
     bf16_raw* dkp = g.dK + (bhS + key) * HD;
@@ -523,12 +474,34 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(BwdArgs g) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------ dQ, 64-query waves
+// ------------------------------------------------------------------------------------------------ the generated 64-wide pair
 // attn_bwd_dq64_kernel: 4 waves x 64 queries (two 32-query chains sharing every K / V / K^T fragment), one wave per SIMD, a
 // generated hand-placed instruction stream: csrc/gen/attn_bwd_dq64.py (design, register map, schedule), checked on the CPU by
 // tests/test_attn_bwd64_emulated.py.  S % 256 == 0; other shapes take attn_bwd_dq_kernel above.
+// attn_bwd_dkv64_kernel: 4 waves x 64 keys (two 32-key chains sharing every Q / dO / Q^T / dO^T fragment), one wave per SIMD,
+// dV^T and dK^T of both chains in all 256 accumulator registers; generated stream: csrc/gen/attn_bwd_dkv64.py.
+// KV (mgx_attn_bwd_kv): the two streams for a sequence padded to g.S = g.Sp = Sa (% 256 == 0); keys and queries >= kv_len
+// (Sa - 256 < kv_len <= Sa) contribute nothing, rows >= kv_len of dQ / dK / dV are stored as zero.  The loops are the unmasked
+// streams' line for line; the masks sit in the iterations outside them ("Masked tail" in gen/attn_bwd_dq64.py and
+// gen/attn_bwd_dkv64.py).  What a launch derives from S and kv_len -- the generators' kv_operands -- is attn_operands.h.
 #include "attn_bwd_dq64_body.inc"
+#include "attn_bwd_dq64kv_body.inc"
+#include "attn_bwd_dkv64_body.inc"
+#include "attn_bwd_dkv64kv_body.inc"
 
+#define LO(x) "s"((unsigned)(x))
+#define HI(x) "s"((unsigned)((x) >> 32))
+// (readfirstlane: the clamps are selected as vector med3, and an "s" operand has to be in a scalar register)
+#define UNIFORM(x) "s"(__builtin_amdgcn_readfirstlane(x))
+
+#define ATTN_BWD_DQ64_OPERANDS                                                                                                  \
+  [tid] "v"(threadIdx.x), [q_lo] LO(qp), [q_hi] HI(qp), [k_lo] LO(kp), [k_hi] HI(kp), [v_lo] LO(vp), [v_hi] HI(vp),              \
+      [kt_lo] LO(ktp), [kt_hi] HI(ktp), [do_lo] LO(dop), [do_hi] HI(dop), [lse_lo] LO(lsep), [lse_hi] HI(lsep), [dl_lo] LO(dlp), \
+      [dl_hi] HI(dlp), [dq_lo] LO(dqp), [dq_hi] HI(dqp), [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)),                      \
+      [cs] "s"(g.scale_log2e), [scale] "s"(g.scale), [nloop] "s"(ops.nloop), [seq] "s"(ops.seq)
+#define ATTN_BWD_DQ64_KV_OPERANDS ATTN_BWD_DQ64_OPERANDS, [kt0] UNIFORM(ops.kt0), [kt1] UNIFORM(ops.kt1), [qlast] UNIFORM(ops.qlast)
+
+template <bool KV>
 __global__ void __launch_bounds__(256, 1) attn_bwd_dq64_kernel(BwdArgs g) {
   const int nq = g.S >> 8;
   int bid = blockIdx.x;
@@ -544,26 +517,20 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_dq64_kernel(BwdArgs g) {
   const unsigned long long lsep = (unsigned long long)(g.lse + bhS + qt * 256);
   const unsigned long long dlp = (unsigned long long)(g.delta + bhS + qt * 256);
   const unsigned long long dqp = (unsigned long long)(g.dQ + (bhS + qt * 256) * HD);
-  const int ntiles = g.S >> 6;
-#define LOHI(x) "s"((unsigned)(x)), "s"((unsigned)((x) >> 32))
-  asm volatile(ATTN_BWD_DQ64_BODY
-               :
-               : [tid] "v"(threadIdx.x), [q_lo] "s"((unsigned)qp), [q_hi] "s"((unsigned)(qp >> 32)), [k_lo] "s"((unsigned)kp),
-                 [k_hi] "s"((unsigned)(kp >> 32)), [v_lo] "s"((unsigned)vp), [v_hi] "s"((unsigned)(vp >> 32)),
-                 [kt_lo] "s"((unsigned)ktp), [kt_hi] "s"((unsigned)(ktp >> 32)), [do_lo] "s"((unsigned)dop),
-                 [do_hi] "s"((unsigned)(dop >> 32)), [lse_lo] "s"((unsigned)lsep), [lse_hi] "s"((unsigned)(lsep >> 32)),
-                 [dl_lo] "s"((unsigned)dlp), [dl_hi] "s"((unsigned)(dlp >> 32)), [dq_lo] "s"((unsigned)dqp),
-                 [dq_hi] "s"((unsigned)(dqp >> 32)), [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)), [cs] "s"(g.scale_log2e),
-                 [scale] "s"(g.scale), [nloop] "s"((ntiles - 2) >> 1), [seq] "s"(g.S)
-               : ATTN_BWD_DQ64_CLOBBERS);
-#undef LOHI
+  const attn_ops::Dq64 ops = attn_ops::dq64(KV, g.S, g.kv_len, qt);
+  if constexpr (KV) asm volatile(ATTN_BWD_DQ64KV_BODY : : ATTN_BWD_DQ64_KV_OPERANDS : ATTN_BWD_DQ64KV_CLOBBERS);
+  else asm volatile(ATTN_BWD_DQ64_BODY : : ATTN_BWD_DQ64_OPERANDS : ATTN_BWD_DQ64_CLOBBERS);
 }
 
-// ------------------------------------------------------------------------------------------------ dK, dV, 64-key waves
-// attn_bwd_dkv64_kernel: 4 waves x 64 keys (two 32-key chains sharing every Q / dO / Q^T / dO^T fragment), one wave per SIMD,
-// dV^T and dK^T of both chains in all 256 accumulator registers; generated stream: csrc/gen/attn_bwd_dkv64.py.
-#include "attn_bwd_dkv64_body.inc"
+#define ATTN_BWD_DKV64_OPERANDS                                                                                                \
+  [tid] "v"(threadIdx.x), [q_lo] LO(qp), [q_hi] HI(qp), [do_lo] LO(dop), [do_hi] HI(dop), [qt_lo] LO(qtp), [qt_hi] HI(qtp),     \
+      [dot_lo] LO(dotp), [dot_hi] HI(dotp), [k_lo] LO(kp), [k_hi] HI(kp), [v_lo] LO(vp), [v_hi] HI(vp), [lse_lo] LO(lsep),      \
+      [lse_hi] HI(lsep), [dl_lo] LO(dlp), [dl_hi] HI(dlp), [dk_lo] LO(dkp), [dk_hi] HI(dkp), [dv_lo] LO(dvp), [dv_hi] HI(dvp),  \
+      [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)), [cs] "s"(g.scale_log2e), [scale] "s"(g.scale),                         \
+      [nis] "s"(g.neg_inv_scale), [nloop] "s"(ops.nloop), [qmax] "s"(ops.qmax), [ldo32] "s"((int)(g.ldo * 64)), [cmax] "s"(ops.cmax)
+#define ATTN_BWD_DKV64_KV_OPERANDS ATTN_BWD_DKV64_OPERANDS, [qk] UNIFORM(ops.qk), [klast] UNIFORM(ops.klast)
 
+template <bool KV>
 __global__ void __launch_bounds__(256, 1) attn_bwd_dkv64_kernel(BwdArgs g) {
   const int nkb = g.S >> 8;
   int bid = blockIdx.x;
@@ -581,113 +548,14 @@ __global__ void __launch_bounds__(256, 1) attn_bwd_dkv64_kernel(BwdArgs g) {
   const unsigned long long dlp = (unsigned long long)(g.delta + bhS);
   const unsigned long long dkp = (unsigned long long)(g.dK + (bhS + kt * 256) * HD);
   const unsigned long long dvp = (unsigned long long)(g.dV + (bhS + kt * 256) * HD);
-  const int nq = g.S >> 5;
-#define LO(x) "s"((unsigned)(x))
-#define HI(x) "s"((unsigned)((x) >> 32))
-  asm volatile(ATTN_BWD_DKV64_BODY
-               :
-               : [tid] "v"(threadIdx.x), [q_lo] LO(qp), [q_hi] HI(qp), [do_lo] LO(dop), [do_hi] HI(dop), [qt_lo] LO(qtp),
-                 [qt_hi] HI(qtp), [dot_lo] LO(dotp), [dot_hi] HI(dotp), [k_lo] LO(kp), [k_hi] HI(kp), [v_lo] LO(vp), [v_hi] HI(vp),
-                 [lse_lo] LO(lsep), [lse_hi] HI(lsep), [dl_lo] LO(dlp), [dl_hi] HI(dlp), [dk_lo] LO(dkp), [dk_hi] HI(dkp),
-                 [dv_lo] LO(dvp), [dv_hi] HI(dvp), [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)), [cs] "s"(g.scale_log2e),
-                 [scale] "s"(g.scale), [nis] "s"(g.neg_inv_scale), [nloop] "s"((nq - 2) >> 1), [qmax] "s"((nq - 1) * 8192),
-                 [ldo32] "s"((int)(g.ldo * 64)), [cmax] "s"((nq - 1) * 128)
-               : ATTN_BWD_DKV64_CLOBBERS);
+  const attn_ops::Dkv64 ops = attn_ops::dkv64(KV, g.S, g.kv_len, kt);
+  if constexpr (KV) asm volatile(ATTN_BWD_DKV64KV_BODY : : ATTN_BWD_DKV64_KV_OPERANDS : ATTN_BWD_DKV64KV_CLOBBERS);
+  else asm volatile(ATTN_BWD_DKV64_BODY : : ATTN_BWD_DKV64_OPERANDS : ATTN_BWD_DKV64_CLOBBERS);
+}
+
 #undef LO
 #undef HI
-}
-
-// ------------------------------------------------------------------------------------------------ masked tail, 64-wide pair
-// attn_bwd_dq64kv_kernel / attn_bwd_dkv64kv_kernel (mgx_attn_bwd_kv): the two streams above for a sequence padded to
-// g.S = g.Sp = Sa (% 256 == 0); keys and queries >= kv_len (Sa - 256 < kv_len <= Sa) contribute nothing, rows >= kv_len of
-// dQ / dK / dV are stored as zero.  The loops are the unmasked streams' line for line; the masks sit in the iterations outside
-// them ("Masked tail" in gen/attn_bwd_dq64.py and gen/attn_bwd_dkv64.py, whose kv_operands the launch code below restates).
-struct BwdKvArgs {
-  BwdArgs g;
-  int kv_len;
-};
-
-#include "attn_bwd_dq64kv_body.inc"
-
-__global__ void __launch_bounds__(256, 1) attn_bwd_dq64kv_kernel(BwdKvArgs a) {
-  const BwdArgs& g = a.g;
-  const int kv_len = a.kv_len;
-  const int nq = g.S >> 8;
-  int bid = blockIdx.x;
-  xcd_remap(bid, nq * g.H * g.B);
-  const int qt = bid % nq, bh = bid / nq;
-  const int b = bh / g.H, hh = bh - b * g.H;
-  const long bhS = (long)bh * g.S;
-  const unsigned long long qp = (unsigned long long)(g.Q + (bhS + qt * 256) * HD);
-  const unsigned long long kp = (unsigned long long)(g.K + bhS * HD);
-  const unsigned long long vp = (unsigned long long)(g.V + bhS * HD);
-  const unsigned long long ktp = (unsigned long long)(g.Kt + (long)bh * HD * g.Sp);
-  const unsigned long long dop = (unsigned long long)(g.dO + (long)b * g.o_bstride + (long)(qt * 256) * g.ldo + hh * HD);
-  const unsigned long long lsep = (unsigned long long)(g.lse + bhS + qt * 256);
-  const unsigned long long dlp = (unsigned long long)(g.delta + bhS + qt * 256);
-  const unsigned long long dqp = (unsigned long long)(g.dQ + (bhS + qt * 256) * HD);
-  // the 64-key tiles walked: those with a valid key, rounded up to a pair, at least four (the loop's last pair is peeled)
-  const int ntiles = max(4, (((kv_len + 63) >> 6) + 1) & ~1);
-  auto cnt = [&](int j) { return 8 + min(32, max(0, kv_len - 32 * j)); };      // 8 + the valid keys of 32-key block j
-  // (readfirstlane: the clamps are selected as vector med3, and an "s" operand has to be in a scalar register)
-  const int kt0 = __builtin_amdgcn_readfirstlane(cnt(0) | cnt(1) << 8 | cnt(2 * ntiles - 6) << 16 | cnt(2 * ntiles - 5) << 24);
-  const int kt1 = __builtin_amdgcn_readfirstlane(cnt(2 * ntiles - 4) | cnt(2 * ntiles - 3) << 8 | cnt(2 * ntiles - 2) << 16 |
-                                                 cnt(2 * ntiles - 1) << 24);
-  const int qlast = __builtin_amdgcn_readfirstlane(min(255, kv_len - 1 - 256 * qt));   // >= 0: the last block holds a valid row
-  asm volatile(ATTN_BWD_DQ64KV_BODY
-               :
-               : [tid] "v"(threadIdx.x), [q_lo] "s"((unsigned)qp), [q_hi] "s"((unsigned)(qp >> 32)), [k_lo] "s"((unsigned)kp),
-                 [k_hi] "s"((unsigned)(kp >> 32)), [v_lo] "s"((unsigned)vp), [v_hi] "s"((unsigned)(vp >> 32)),
-                 [kt_lo] "s"((unsigned)ktp), [kt_hi] "s"((unsigned)(ktp >> 32)), [do_lo] "s"((unsigned)dop),
-                 [do_hi] "s"((unsigned)(dop >> 32)), [lse_lo] "s"((unsigned)lsep), [lse_hi] "s"((unsigned)(lsep >> 32)),
-                 [dl_lo] "s"((unsigned)dlp), [dl_hi] "s"((unsigned)(dlp >> 32)), [dq_lo] "s"((unsigned)dqp),
-                 [dq_hi] "s"((unsigned)(dqp >> 32)), [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)), [cs] "s"(g.scale_log2e),
-                 [scale] "s"(g.scale), [nloop] "s"((ntiles - 4) >> 1), [seq] "s"(64 * ntiles), [kt0] "s"(kt0), [kt1] "s"(kt1),
-                 [qlast] "s"(qlast)
-               : ATTN_BWD_DQ64KV_CLOBBERS);
-}
-
-#include "attn_bwd_dkv64kv_body.inc"
-
-__global__ void __launch_bounds__(256, 1) attn_bwd_dkv64kv_kernel(BwdKvArgs a) {
-  const BwdArgs& g = a.g;
-  const int kv_len = a.kv_len;
-  const int nkb = g.S >> 8;
-  int bid = blockIdx.x;
-  xcd_remap(bid, nkb * g.H * g.B);
-  const int kt = bid % nkb, bh = bid / nkb;
-  const int b = bh / g.H, hh = bh - b * g.H;
-  const long bhS = (long)bh * g.S;
-  const unsigned long long qp = (unsigned long long)(g.Q + bhS * HD);
-  const unsigned long long dop = (unsigned long long)(g.dO + (long)b * g.o_bstride + hh * HD);
-  const unsigned long long qtp = (unsigned long long)(g.Qt + (long)bh * HD * g.Sp);
-  const unsigned long long dotp = (unsigned long long)(g.dOt + (long)bh * HD * g.Sp);
-  const unsigned long long kp = (unsigned long long)(g.K + (bhS + kt * 256) * HD);
-  const unsigned long long vp = (unsigned long long)(g.V + (bhS + kt * 256) * HD);
-  const unsigned long long lsep = (unsigned long long)(g.lse + bhS);
-  const unsigned long long dlp = (unsigned long long)(g.delta + bhS);
-  const unsigned long long dkp = (unsigned long long)(g.dK + (bhS + kt * 256) * HD);
-  const unsigned long long dvp = (unsigned long long)(g.dV + (bhS + kt * 256) * HD);
-  // the 32-query blocks walked: those with a valid query, rounded up to a pair, at least four (the loop's last pair is peeled)
-  const int nq = max(4, (((kv_len + 31) >> 5) + 1) & ~1);
-  auto cnt = [&](int j) { return 8 + min(32, max(0, kv_len - 32 * j)); };      // 8 + the valid queries of 32-query block j
-  const int qk = __builtin_amdgcn_readfirstlane(cnt(0) | cnt(nq - 3) << 8 | cnt(nq - 2) << 16 | cnt(nq - 1) << 24);
-  const int klast = __builtin_amdgcn_readfirstlane(min(255, kv_len - 1 - 256 * kt));   // >= 0: the last block holds a valid row
-#define LO(x) "s"((unsigned)(x))
-#define HI(x) "s"((unsigned)((x) >> 32))
-  asm volatile(ATTN_BWD_DKV64KV_BODY
-               :
-               : [tid] "v"(threadIdx.x), [q_lo] LO(qp), [q_hi] HI(qp), [do_lo] LO(dop), [do_hi] HI(dop), [qt_lo] LO(qtp),
-                 [qt_hi] HI(qtp), [dot_lo] LO(dotp), [dot_hi] HI(dotp), [k_lo] LO(kp), [k_hi] HI(kp), [v_lo] LO(vp), [v_hi] HI(vp),
-                 [lse_lo] LO(lsep), [lse_hi] HI(lsep), [dl_lo] LO(dlp), [dl_hi] HI(dlp), [dk_lo] LO(dkp), [dk_hi] HI(dkp),
-                 [dv_lo] LO(dvp), [dv_hi] HI(dvp), [sp2] "s"(g.Sp * 2), [ldo2] "s"((int)(g.ldo * 2)), [cs] "s"(g.scale_log2e),
-                 [scale] "s"(g.scale), [nis] "s"(g.neg_inv_scale), [nloop] "s"((nq - 4) >> 1), [qmax] "s"((nq - 1) * 8192),
-                 [ldo32] "s"((int)(g.ldo * 64)), [cmax] "s"((nq - 1) * 128), [qk] "s"(qk), [klast] "s"(klast)
-               : ATTN_BWD_DKV64KV_CLOBBERS);
-#undef LO
-#undef HI
-}
-
+#undef UNIFORM
 }  // namespace
 
 // Which backward kernels a problem gets: 1 = the generated 64-wide pair, 0 = the 8-wave pair.  The ONE predicate of mgx_attn_bwd
@@ -699,38 +567,47 @@ static bool attn_bwd_wide(int B, int H, int S, int Sp, long ldo, long o_bstride)
   return w64 && S % 256 == 0 && Sp == S && ldo * 2 * 256 < (1L << 31) && ldo * 2 < (1L << 24) && Sp * 2 < (1L << 24);
 }
 
+// The masked-tail backward takes a problem when the 64-wide pair takes it at S = Sp = Sa and kv_len lies in the last 256 rows.
+// The ONE predicate of mgx_attn_bwd_kv and of the mgx_attn_bwd_kv_path query.  There is no other kernel behind it.
+static bool attn_bwd_kv_wide(int B, int H, int Sa, int kv_len, long ldo, long o_bstride) {
+  return B > 0 && H > 0 && Sa > 0 && kv_len > Sa - 256 && kv_len <= Sa && o_bstride >= (long)Sa * ldo &&
+         attn_bwd_wide(B, H, Sa, Sa, ldo, o_bstride);
+}
+
+// What both entry points begin with: the checks, the kernels' arguments, delta and dOt.  `taken` false (mgx_attn_bwd_kv only)
+// refuses a well-formed call: 1, nothing launched.
+static int attn_bwd_begin(BwdArgs& g, const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* Qt,
+                          const uint16_t* Kt, const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt,
+                          uint16_t* dQ, uint16_t* dK, uint16_t* dV, int B, int H, int S, int Sp, int kv_len, long ldo,
+                          long o_bstride, float scale, bool taken, hipStream_t st) {
+  MGX_REQUIRE(Q && K && V && Qt && Kt && O && dO && lse && delta && dOt && dQ && dK && dV, "null operand");
+  MGX_REQUIRE(ldo % 8 == 0 && o_bstride % 8 == 0, "dO rows must be 16-byte aligned");
+  if (!taken) return 1;
+  MGX_REQUIRE(B > 0 && H > 0 && S > 0 && Sp >= S && Sp % 64 == 0, "bad sizes");
+  g.Q = Q; g.K = K; g.V = V; g.Qt = Qt; g.Kt = Kt; g.dO = dO; g.dOt = dOt; g.lse = lse; g.delta = delta;
+  g.dQ = dQ; g.dK = dK; g.dV = dV; g.B = B; g.H = H; g.S = S; g.Sp = Sp; g.ldo = ldo; g.o_bstride = o_bstride;
+  g.scale = scale; g.scale_log2e = scale * 1.4426950408889634f; g.neg_inv_scale = -1.0f / scale;
+  g.kv_len = kv_len;
+  attn_bwd_prep_kernel<<<dim3(Sp / 64, H, B), 256, 0, st>>>(O, dO, ldo, o_bstride, delta, dOt, H, S, Sp, kv_len);
+  return MGX_OK;
+}
+
 extern "C" int mgx_attn_bwd(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* Qt, const uint16_t* Kt,
                             const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt,
                             uint16_t* dQ, uint16_t* dK, uint16_t* dV, int B, int H, int S, int Sp, long ldo, long o_bstride,
                             float scale, void* stream) {
-  MGX_REQUIRE(Q && K && V && Qt && Kt && O && dO && lse && delta && dOt && dQ && dK && dV, "null operand");
-  MGX_REQUIRE(B > 0 && H > 0 && S > 0 && Sp >= S && Sp % 64 == 0, "bad sizes");
-  MGX_REQUIRE(ldo % 8 == 0 && o_bstride % 8 == 0, "dO rows must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  attn_bwd_prep_kernel<<<dim3(Sp / 64, H, B), 256, 0, st>>>(O, dO, ldo, o_bstride, delta, dOt, H, S, Sp);
   BwdArgs g;
-  g.Q = Q; g.K = K; g.V = V; g.Qt = Qt; g.Kt = Kt; g.dO = dO; g.dOt = dOt; g.lse = lse; g.delta = delta;
-  g.dQ = dQ; g.dK = dK; g.dV = dV; g.B = B; g.H = H; g.S = S; g.Sp = Sp; g.ldo = ldo; g.o_bstride = o_bstride;
-  g.scale = scale; g.scale_log2e = scale * 1.4426950408889634f; g.neg_inv_scale = -1.0f / scale;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * DKV_STAGE + 65536);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * DQ_STAGE);
-    attr = true;
-  }
+  if (const int rc = attn_bwd_begin(g, Q, K, V, Qt, Kt, O, dO, lse, delta, dOt, dQ, dK, dV, B, H, S, Sp, S, ldo, o_bstride, scale,
+                                    true, st))
+    return rc;
   const int nb = cdiv(S, 256) * H * B;
   if (attn_bwd_wide(B, H, S, Sp, ldo, o_bstride)) {
-    static bool attr64 = false;
-    if (!attr64) {
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dq64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
-      (void)hipFuncSetAttribute((const void*)attn_bwd_dkv64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 149504);
-      attr64 = true;
-    }
-    attn_bwd_dkv64_kernel<<<nb, 256, 149504, st>>>(g);
-    attn_bwd_dq64_kernel<<<nb, 256, 98304, st>>>(g);
+    launch_lds<attn_bwd_dkv64_kernel<false>, 149504>(nb, 256, st, g);
+    launch_lds<attn_bwd_dq64_kernel<false>, 98304>(nb, 256, st, g);
   } else {
-    attn_bwd_dkv_kernel<<<nb, 512, 2 * DKV_STAGE + 65536, st>>>(g);   // + wave-private V fragments
-    attn_bwd_dq_kernel<<<nb, 512, 2 * DQ_STAGE, st>>>(g);
+    launch_lds<attn_bwd_dkv_kernel, 2 * DKV_STAGE + 65536>(nb, 512, st, g);   // + wave-private V fragments
+    launch_lds<attn_bwd_dq_kernel, 2 * DQ_STAGE>(nb, 512, st, g);
   }
   MGX_CHECK_LAUNCH();
   return MGX_OK;
@@ -741,37 +618,18 @@ extern "C" int mgx_attn_bwd_path(int B, int H, int S, int Sp, long ldo, long o_b
   return attn_bwd_wide(B, H, S, Sp, ldo, o_bstride) ? 1 : 0;
 }
 
-// The masked-tail backward takes a problem when the 64-wide pair takes it at S = Sp = Sa and kv_len lies in the last 256 rows.
-// The ONE predicate of mgx_attn_bwd_kv and of the mgx_attn_bwd_kv_path query.  There is no other kernel behind it.
-static bool attn_bwd_kv_wide(int B, int H, int Sa, int kv_len, long ldo, long o_bstride) {
-  return B > 0 && H > 0 && Sa > 0 && kv_len > Sa - 256 && kv_len <= Sa && o_bstride >= (long)Sa * ldo &&
-         attn_bwd_wide(B, H, Sa, Sa, ldo, o_bstride);
-}
-
 extern "C" int mgx_attn_bwd_kv(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* Qt, const uint16_t* Kt,
                                const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt,
                                uint16_t* dQ, uint16_t* dK, uint16_t* dV, int B, int H, int Sa, int kv_len, long ldo,
                                long o_bstride, float scale, void* stream) {
-  MGX_REQUIRE(Q && K && V && Qt && Kt && O && dO && lse && delta && dOt && dQ && dK && dV, "null operand");
-  MGX_REQUIRE(ldo % 8 == 0 && o_bstride % 8 == 0, "dO rows must be 16-byte aligned");
-  if (!attn_bwd_kv_wide(B, H, Sa, kv_len, ldo, o_bstride)) return 1;   // nothing launched: the caller's unpadded path
   hipStream_t st = (hipStream_t)stream;
-  attn_bwd_prep_kv_kernel<<<dim3(Sa / 64, H, B), 256, 0, st>>>(O, dO, ldo, o_bstride, delta, dOt, H, Sa, kv_len);
-  BwdKvArgs a;
-  BwdArgs& g = a.g;
-  g.Q = Q; g.K = K; g.V = V; g.Qt = Qt; g.Kt = Kt; g.dO = dO; g.dOt = dOt; g.lse = lse; g.delta = delta;
-  g.dQ = dQ; g.dK = dK; g.dV = dV; g.B = B; g.H = H; g.S = Sa; g.Sp = Sa; g.ldo = ldo; g.o_bstride = o_bstride;
-  g.scale = scale; g.scale_log2e = scale * 1.4426950408889634f; g.neg_inv_scale = -1.0f / scale;
-  a.kv_len = kv_len;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dq64kv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_dkv64kv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 149504);
-    attr = true;
-  }
+  BwdArgs g;
+  if (const int rc = attn_bwd_begin(g, Q, K, V, Qt, Kt, O, dO, lse, delta, dOt, dQ, dK, dV, B, H, Sa, Sa, kv_len, ldo, o_bstride,
+                                    scale, attn_bwd_kv_wide(B, H, Sa, kv_len, ldo, o_bstride), st))
+    return rc;                                                           // 1: nothing launched, the caller's unpadded path
   const int nb = (Sa / 256) * H * B;
-  attn_bwd_dkv64kv_kernel<<<nb, 256, 149504, st>>>(a);
-  attn_bwd_dq64kv_kernel<<<nb, 256, 98304, st>>>(a);
+  launch_lds<attn_bwd_dkv64_kernel<true>, 149504>(nb, 256, st, g);
+  launch_lds<attn_bwd_dq64_kernel<true>, 98304>(nb, 256, st, g);
   MGX_CHECK_LAUNCH();
   return MGX_OK;
 }

@@ -154,12 +154,8 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_fp8_kernel(AttnF8Args g) {
   asm volatile("" : "+v"(one_e8m0));
 
   const int nq = (g.S + QB - 1) / QB;
-  const int nwg = nq * g.H * g.B;
   int bid = blockIdx.x;
-  {   // the q-tiles of one (b, head) stay on one XCD so its K/V stay in that L2
-    const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-  }
+  xcd_remap(bid, nq * g.H * g.B);   // the q-tiles of one (b, head) stay on one XCD so its K/V stay in that L2
   const int qt = bid % nq;
   const int bh = bid / nq;
   const int b = bh / g.H, hh = bh - b * g.H;
@@ -312,13 +308,9 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_fp8_kernel(AttnF8Args g) {
 #pragma unroll
       for (int i4 = 0; i4 < 4; ++i4) {
         const int d = dt * 32 + 8 * i4 + 4 * h;
-        typedef float f32x2_t __attribute__((ext_vector_type(2)));
-        typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-        const f32x2_t v0 = {o[dt][4 * i4] * inv, o[dt][4 * i4 + 1] * inv};
-        const f32x2_t v1 = {o[dt][4 * i4 + 2] * inv, o[dt][4 * i4 + 3] * inv};
         uint2 w;
-        w.x = __builtin_bit_cast(uint32_t, __builtin_convertvector(v0, bf16x2_t));
-        w.y = __builtin_bit_cast(uint32_t, __builtin_convertvector(v1, bf16x2_t));
+        w.x = pack_bf16(o[dt][4 * i4] * inv, o[dt][4 * i4 + 1] * inv);
+        w.y = pack_bf16(o[dt][4 * i4 + 2] * inv, o[dt][4 * i4 + 3] * inv);
         *reinterpret_cast<uint2*>(op + d) = w;
       }
     if (g.lse && h == 0)   // sum_k 2^(s c) = 2^(m c - 2) * l

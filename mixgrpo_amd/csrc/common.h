@@ -68,4 +68,26 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  const f32x2_t v = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));   // one v_cvt_pk_bf16_f32
+}
+
+// XCD-aware workgroup order (workgroups go round-robin over the 8 XCDs): consecutive remapped ids share an XCD, so the
+// q-tiles / key blocks of one (batch, head) run on one XCD and its operands stay in that L2
+__device__ __forceinline__ void xcd_remap(int& bid, int nwg) {
+  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+  bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
+}
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Launch `Kernel` with LDS bytes of dynamic LDS; the first launch of each kernel raises its limit (above 64 KiB it must)
+template <auto Kernel, int LDS, typename Args>
+static inline void launch_lds(int grid, int block, hipStream_t st, const Args& args) {
+  static const hipError_t attr = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  (void)attr;
+  Kernel<<<grid, block, LDS, st>>>(args);
+}

@@ -535,11 +535,11 @@ def generate(kv=False):
 
 
 def kv_operands(kv_len, kt=0):
-    """kv: what the launcher derives from kv_len for the workgroup of key block `kt` (csrc/attention_bwd.hip restates it; the
-    CPU tests feed the interpreter from here): the 32-query blocks walked -- those with a valid query, rounded up to a pair, at
-    least four --, the loop's trips (its last pair is peeled), the clamps of the Q | dO and lse | delta fetches, qk = four
-    bytes, lowest first: 8 + the valid queries (0 .. 32) of the first block and of the last three, and the block's last valid
-    key row."""
+    """kv: what the launcher derives from kv_len for the workgroup of key block `kt` (in C++: dkv64 of csrc/attn_operands.h,
+    which the kernel calls and mgx_attn_kv_operands returns -- the tests hold it equal to this; the CPU tests feed the
+    interpreter from here): the 32-query blocks walked -- those with a valid query, rounded up to a pair, at least four --,
+    the loop's trips (its last pair is peeled), the clamps of the Q | dO and lse | delta fetches, qk = four bytes, lowest
+    first: 8 + the valid queries (0 .. 32) of the first block and of the last three, and the block's last valid key row."""
     nq = max(4, ((kv_len + 31) // 32 + 1) & ~1)
     c = lambda i: 8 + min(32, max(0, kv_len - 32 * i))
     return dict(nloop=(nq - 4) // 2, qmax=(nq - 1) * 8192, cmax=(nq - 1) * 128,

@@ -363,11 +363,12 @@ def generate(kv=False):
 
 
 def kv_operands(kv_len, qt=0):
-    """kv: what the launcher derives from kv_len for the workgroup of q-tile `qt` (csrc/attention_bwd.hip restates it; the CPU
-    tests feed the interpreter from here): the 64-key tiles walked -- those with a valid key, rounded up to a pair, at least
-    four --, the loop's trips (its last pair is peeled), the length the window fetch is clamped at, kt0 / kt1 = four bytes
-    each, lowest first: 8 + the valid keys (0 .. 32) of the 32-key blocks of the first tile and of the last three, and the
-    block's last valid query row."""
+    """kv: what the launcher derives from kv_len for the workgroup of q-tile `qt` (in C++: dq64 of csrc/attn_operands.h, which
+    the kernel calls and mgx_attn_kv_operands returns -- the tests hold it equal to this; the CPU tests feed the interpreter
+    from here): the 64-key tiles walked -- those with a valid key, rounded up to a pair, at least four --, the loop's trips
+    (its last pair is peeled), the length the window fetch is clamped at, kt0 / kt1 = four bytes each, lowest first: 8 + the
+    valid keys (0 .. 32) of the 32-key blocks of the first tile and of the last three, and the block's last valid query
+    row."""
     nt = max(4, ((kv_len + 63) // 64 + 1) & ~1)
     c = lambda j: 8 + min(32, max(0, kv_len - 32 * j))
     pack = lambda js: sum(c(j) << (8 * i) for i, j in enumerate(js))

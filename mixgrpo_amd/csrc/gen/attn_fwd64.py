@@ -662,10 +662,11 @@ def generate(diag=False, acc=False, timing_only=(), kv_tail=False):
 
 
 def kv_operands(kv_len):
-    """kv_tail: what the launcher derives from kv_len (csrc/attention.hip restates it; the CPU tests feed the interpreter from
-    here): the tiles walked -- those with a valid key, rounded up to a pair, at least four --, the loop's trips (its last pair
-    is peeled), the clamps of the tile fetch, kt = four bytes, lowest first: 8 + the valid keys (0 .. 64) of the first tile
-    and of the last three, and the last valid row."""
+    """kv_tail: what the launcher derives from kv_len (in C++: fwd64 of csrc/attn_operands.h, which the kernel calls and
+    mgx_attn_kv_operands returns -- the tests hold it equal to this; the CPU tests feed the interpreter from here): the tiles
+    walked -- those with a valid key, rounded up to a pair, at least four --, the loop's trips (its last pair is peeled), the
+    clamps of the tile fetch, kt = four bytes, lowest first: 8 + the valid keys (0 .. 64) of the first tile and of the last
+    three, and the last valid row."""
     nt = max(4, ((kv_len + 63) // 64 + 1) & ~1)
     kt = lambda i: 8 + min(64, max(0, kv_len - 64 * i))
     return dict(nloop=(nt - 4) // 2, kmax=(nt - 1) * SLOT, vmax=(nt - 1) * 128,

@@ -134,21 +134,37 @@ def _loop(text):
 
 
 # ------------------------------------------------------------------------------------------------ the text of the streams
+def _macro(src, name):
+    """The replacement text of `#define name` in src, continuation lines joined."""
+    import re
+    m = re.search(r"^#define %s[ \t]+((?:.*\\\n)*.*)$" % name, src, flags=re.M)
+    assert m, f"#define {name} not found"
+    return m.group(1).replace("\\\n", " ")
+
+
 def test_new_bodies_fit_what_the_kernels_include():
     """The two new bodies are build products (written by build._generate() through the registered generators, not committed):
     attention_bwd.hip includes them by the names the generators write them under and expands the macros they define, and
-    every `%[name]` operand of a stream is bound by its kernel's asm statement."""
+    every `%[name]` operand of a stream is bound by the operand macro of its kernel's asm statement (the masked streams': the
+    unmasked one's operands and the `_KV` extension)."""
     import re
     from mixgrpo_amd.csrc import gen
     assert {"attn_bwd_dq64", "attn_bwd_dkv64"} <= set(gen.GENERATORS)
     src = open(os.path.join(HERE, "..", "mixgrpo_amd", "csrc", "attention_bwd.hip")).read()
-    for G, macro in ((GQ, "ATTN_BWD_DQ64KV"), (GK, "ATTN_BWD_DKV64KV")):
+    for G, macro, ops in ((GQ, "ATTN_BWD_DQ64KV", "ATTN_BWD_DQ64"), (GK, "ATTN_BWD_DKV64KV", "ATTN_BWD_DKV64")):
         assert f'#include "{os.path.basename(G.OUT_BODY_KV)}"' in src
         text = G.render(kv=True)
         assert f"#define {macro}_BODY" in text and f"#define {macro}_CLOBBERS" in text
-        stmt = src[src.index(f"asm volatile({macro}_BODY"):src.index(f": {macro}_CLOBBERS")]
-        bound = set(re.findall(r"\[(\w+)\]", stmt))
+        # the statement that expands the masked body takes the _KV operand macro, which extends the unmasked one
+        assert re.search(r"asm volatile\(%s_BODY\s*:\s*:\s*%s_KV_OPERANDS\s*:\s*%s_CLOBBERS\)" % (macro, ops, macro), src)
+        kv_ops = _macro(src, f"{ops}_KV_OPERANDS")
+        assert re.match(r"%s_OPERANDS\s*," % ops, kv_ops)
+        bound = set(re.findall(r"\[(\w+)\]", kv_ops)) | set(re.findall(r"\[(\w+)\]", _macro(src, f"{ops}_OPERANDS")))
         assert set(re.findall(r"%\[(\w+)\]", text)) <= bound, set(re.findall(r"%\[(\w+)\]", text)) - bound
+        # ... and the unmasked statement binds the unmasked stream's
+        assert re.search(r"asm volatile\(%s_BODY\s*:\s*:\s*%s_OPERANDS\s*:\s*%s_CLOBBERS\)" % (ops, ops, ops), src)
+        plain = set(re.findall(r"\[(\w+)\]", _macro(src, f"{ops}_OPERANDS")))
+        assert set(re.findall(r"%\[(\w+)\]", G.render())) <= plain
 
 
 def test_existing_bodies_do_not_change_with_the_variants():
@@ -188,8 +204,7 @@ def test_masks_sit_outside_the_loops():
 
 
 def test_operands_of_the_launcher():
-    """kv_operands of both generators (restated in csrc/attention_bwd.hip): key tiles / query blocks without a valid row are
-    dropped in pairs, never below four."""
+    """kv_operands of both generators: key tiles / query blocks without a valid row are dropped in pairs, never below four."""
     nt = lambda kv: GQ.kv_operands(kv)["seq"] // 64
     assert [nt(2560 - d) for d in (0, 23, 64, 100, 200, 255)] == [40, 40, 40, 40, 38, 38]
     assert [nt(kv) for kv in (1, 64, 129, 256, 257, 384, 385)] == [4, 4, 4, 4, 6, 6, 8]
@@ -204,9 +219,21 @@ def test_operands_of_the_launcher():
     assert (o["nloop"], o["klast"], o["cmax"], list(o["qk"].to_bytes(4, "little"))) == (38, 232, 79 * 128, [40, 40, 40, 8 + 9])
     o = GK.kv_operands(56, 0)
     assert (o["nloop"], o["klast"], list(o["qk"].to_bytes(4, "little"))) == (0, 55, [40, 8 + 24, 8, 8])
-    src = open(os.path.join(HERE, "..", "mixgrpo_amd", "csrc", "attention_bwd.hip")).read()
-    assert "max(4, (((kv_len + 63) >> 6) + 1) & ~1)" in src and "max(4, (((kv_len + 31) >> 5) + 1) & ~1)" in src
-    assert "8 + min(32, max(0, kv_len - 32 * j))" in src
+
+
+def test_the_kernels_derive_the_same_operands():
+    """What attn_bwd_dq64_kernel<true> and attn_bwd_dkv64_kernel<true> are launched with -- dq64 and dkv64 of
+    csrc/attn_operands.h, the functions the kernels call, returned by the host query mgx_attn_kv_operands (no GPU needed) --
+    is kv_operands for every kv_len up to 1024 and every 256-row block that holds a valid row."""
+    import ctypes
+    from mixgrpo_amd import _lib
+    h = _lib.lib()
+    out = (ctypes.c_int * 5)()
+    for stream, G, names in ((1, GQ, ("nloop", "seq", "kt0", "kt1", "qlast")), (2, GK, ("nloop", "qmax", "cmax", "qk", "klast"))):
+        for kv_len in range(1, 1025):
+            for block in range((kv_len + 255) // 256):
+                assert h.mgx_attn_kv_operands(stream, kv_len, block, out, 5) == 5
+                assert dict(zip(names, out)) == G.kv_operands(kv_len, block), (stream, kv_len, block)
 
 
 # ------------------------------------------------------------------------------------------------ interpreted

@@ -198,8 +198,8 @@ def test_emulated_walk_needs_stride_over_nq_below_heads():
     assert rel < 4e-3 and lse_err < 1e-5
 
 
-def test_dispatch_guard_matches_the_walk():
-    """The host-side guard of csrc/attention.hip restated: grid = min(256, blocks), stride = grid / 8 (or grid), and the
+def test_dispatch_guard_matches_the_walk(monkeypatch):
+    """The host-side guard of csrc/attention.hip: grid = min(256, blocks), stride = grid / 8 (or grid), and the
     64-wide kernel is taken only when stride / nq < H.  FLUX shapes pass; the advisor's failing shapes do not."""
     def walk_ok(S, H, B):
         nq = S // 256
@@ -210,6 +210,10 @@ def test_dispatch_guard_matches_the_walk():
     assert walk_ok(4608, 24, 8) and walk_ok(4608, 24, 1) and walk_ok(1536, 24, 4) and walk_ok(768, 24, 7)
     assert not walk_ok(256, 24, 11)            # stride 32, nq 1: 32 >= 24
     assert not walk_ok(512, 16, 9)             # stride 32, nq 2: 16 >= 16
-    import re, os
-    src = open(os.path.join(os.path.dirname(__file__), "..", "mixgrpo_amd", "csrc", "attention.hip")).read()
-    assert re.search(r"walk_ok = S >= 256 && stride64 / \(S / 256\) < H", src)
+    # the library's own predicate (mgx_attn_fwd_path: the one attn_fwd_any dispatches on; host code, no GPU needed)
+    from mixgrpo_amd import _lib
+    monkeypatch.delenv("MGX_ATTN_W64", raising=False)
+    h = _lib.lib()
+    path = lambda S, H, B: h.mgx_attn_fwd_path(B, H, S, S, H * 128, S * H * 128)
+    for S, H, B in ((4608, 24, 8), (4608, 24, 1), (1536, 24, 4), (768, 24, 7), (256, 24, 11), (512, 16, 9)):
+        assert path(S, H, B) == int(walk_ok(S, H, B)), (S, H, B)

@@ -141,7 +141,7 @@ def test_masks_sit_in_the_peeled_iterations_only():
 
 
 def test_operands_of_the_launcher():
-    """kv_operands (restated in csrc/attention.hip): tiles without a valid key are dropped in pairs, never below four."""
+    """kv_operands: tiles without a valid key are dropped in pairs, never below four."""
     nt = lambda kv: G.kv_operands(kv)["kmax"] // 16384 + 1
     assert [nt(2560 - d) for d in TAILS] == [40, 40, 40, 40, 38, 38]
     assert [nt(kv) for kv in (1, 64, 129, 256, 257, 384, 385)] == [4, 4, 4, 4, 6, 6, 8]
@@ -149,8 +149,21 @@ def test_operands_of_the_launcher():
     assert (o["nloop"], list(o["kt"].to_bytes(4, "little"))) == (18, [72, 72, 72, 8 + 41])
     o = G.kv_operands(100)
     assert (o["nloop"], list(o["kt"].to_bytes(4, "little"))) == (0, [72, 8 + 36, 8, 8])
-    src = open(os.path.join(HERE, "..", "mixgrpo_amd", "csrc", "attention.hip")).read()
-    assert "max(4, (((g.kv_len + 63) >> 6) + 1) & ~1)" in src and "8 + min(64, max(0, g.kv_len - 64 * t))" in src
+
+
+def test_the_kernel_derives_the_same_operands():
+    """What attn_fwd64_kernel<true, true> is launched with -- fwd64 of csrc/attn_operands.h, the function the kernel calls,
+    returned by the host query mgx_attn_kv_operands (no GPU needed) -- is kv_operands for every kv_len up to 1024."""
+    import ctypes
+    from mixgrpo_amd import _lib
+    h = _lib.lib()
+    names = ("nloop", "kmax", "vmax", "kt", "kvm1")
+    out = (ctypes.c_int * 5)()
+    for kv_len in range(1, 1025):
+        assert h.mgx_attn_kv_operands(0, kv_len, 0, out, 5) == 5
+        assert dict(zip(names, out)) == G.kv_operands(kv_len), kv_len
+    for bad in ((3, 100, 0, out, 5), (-1, 100, 0, out, 5), (0, 0, 0, out, 5), (0, 100, 0, out, 4), (0, 100, 0, None, 5)):
+        assert h.mgx_attn_kv_operands(*bad) == -1, bad
 
 
 # ------------------------------------------------------------------------------------------------ interpreted
