@@ -185,19 +185,16 @@ int mgx_linear_bf16_t(const uint16_t* X, const uint16_t* W, const uint16_t* bias
                       long ldx, long ldw, long ld_ct, long tok_rpb, long ct_bstride, float* sk_workspace,
                       long sk_workspace_elems, void* stream);
 
-/* TWO such problems with equal N, K, epilogue and leading dimensions in ONE launch of the persistent kernel: the text- and the
- * image-stream Linear of a FLUX double block, which diffusers issues as separate nn.Linear calls (to_q/k/v | add_q/k/v_proj,
- * to_out | to_add_out, ff | ff_context; call sites fastvideo/utils/sampling_utils.py:68-82, train_grpo_flux.py:134-144,600).
- * Problem 1's M1 rows come first in the tile walk, so the text stream's few tile rows ride the image stream's rounds.
- * Grouped when M1 % 256 == 0, the epilogue is not MGX_EPI_F32_ACC, the two A operands lie within 4 GiB of each other and so do
- * the two W operands (same activation buffer, same block of the parameter store) and the problem is large enough for the persistent kernel; otherwise
- * the call issues the two problems one after the other (mgx_gemm_bf16_sk) -- same results either way, bit for bit per tile. */
-int mgx_gemm_bf16_pair(const uint16_t* A1, const uint16_t* W1, const uint16_t* bias1, void* C1, const uint16_t* gate1,
-                       uint16_t* aux1, int M1, long a1_rpb, long a1_bstride, long c1_rpb, long c1_bstride,
-                       const uint16_t* A2, const uint16_t* W2, const uint16_t* bias2, void* C2, const uint16_t* gate2,
-                       uint16_t* aux2, int M2, long a2_rpb, long a2_bstride, long c2_rpb, long c2_bstride, int N, int K,
-                       long lda, long ldw, long ldc, long ldaux, long gate_ld, int epilogue, float beta,
-                       float* sk_workspace, long sk_workspace_elems, void* stream);
+/* What mgx_gemm_bf16_sk launches for dense operands (lda = ldw = K) of this shape, with (stream_k != 0) or without a
+ * workspace: the plan the kernels themselves walk (csrc/gemm_plan.h), for tests and tools.  No GPU needed.
+ * mgx_gemm_plan: out[0..5] = kernel family (0: 128x128 tiles, 1: persistent 256x256), grid, band, sk_minparts, fix-up
+ * blocks (0: nothing is split), XCDs that split their tail (bit x: XCD x); returns 6.
+ * mgx_gemm_plan_units, fixup == 0: workgroup `index` of the main kernel; returns its number of units, unit i =
+ * out[5 i .. 5 i + 4] = (m0, n0, first K-tile, end K-tile, partial: 1 = its sums go to workspace slot `index`).
+ * fixup != 0: fix-up block `index`; returns the number of workspace slots it adds (0: the block is idle), out[0..1] = (m0, n0)
+ * of the tile it finishes, out[2 ..] = the slots in the order it adds them.  Both return -1 on a bad argument. */
+int mgx_gemm_plan(int M, int N, int K, int stream_k, int* out, int cap);
+int mgx_gemm_plan_units(int M, int N, int K, int stream_k, int fixup, int index, int* out, int cap);
 
 /* out[N, ld_out] = in[M, N]^T (bf16; columns M..ld_out-1 are zero-filled) and, optionally, fp32 column sums
  * colsum_out[n] = beta*colsum_out[n] + sum_m in[m, n] (bias gradients) via a deterministic two-stage reduction;

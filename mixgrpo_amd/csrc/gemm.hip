@@ -10,18 +10,21 @@
 // The MFMA is issued with the weight fragment as the A operand so that each lane ends up with 4 consecutive
 // output features of one token: 8-byte bf16 stores, and bias/gate vectors are per-register constants.
 // blockIdx is remapped so that the 8 XCDs each own a contiguous band of tiles (private L2 reuse of W/A panels).
+// Which kernel takes a problem, the order of the tiles and the stream-K split of the persistent kernel's last round are derived
+// in gemm_plan.h, for the kernels, launch() and the host queries mgx_gemm_plan / mgx_gemm_plan_units alike.
 //
 // "Row-batched" addressing (rpb, bstride) lets the text and image streams live inside one joint
 // [B, S, d] residual buffer: row m -> base + (m / rpb) * bstride + (m % rpb) * ld.
 #include "../../include/mixgrpo_hip.h"
 #include "common.h"
+#include "gemm_plan.h"
 
 #include <cmath>
 #include <cstdlib>
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
+constexpr int BM = 128, BN = 128, BK = gemm_plan::BK;
 constexpr int NT = 256;
 
 struct RowMap {
@@ -66,18 +69,6 @@ struct GemmArgs {
   // sk_minparts = split an XCD's last, partial round only if each of its tiles can then be cut into at least this many parts
   float* sk_ws;
   int sk_minparts;
-  // second problem of a PAIR launch (mgx_gemm_bf16_pair; the text- and image-stream Linear of a double block): rows
-  // m_split.. of the tile grid (m_split % 256 == 0; 0: no pair) are rows 0.. of a problem with its own operands.  Same N, K,
-  // epilogue and leading dimensions.  A2 / W2 are reached through 32-bit offsets from A / W (both streams' operands live in the
-  // same buffers), so the K-loop is the single-problem loop; only the per-tile offsets and the epilogue's operands differ.
-  int m_split;
-  long a1_off, w1_off;    // elements from A / W (= the lower of the two problems' pointers) to problem 1's first element
-  long a2_off, w2_off;    // ... and to problem 2's
-  RowMap a2, c2;
-  void* C2;
-  const bf16_raw* bias2;
-  const bf16_raw* gate2;
-  bf16_raw* aux2;
   // transposed-output Linear (mgx_linear_bf16_t; EPI_BIAS, persistent kernel, 16-byte epilogue only): the roles are swapped -- A =
   // the weight rows (M = output features), W = the activations (N = tokens) -- so C[feature][token] comes out token-contiguous:
   // V^T of the attention without a transposing pass.  bias_rows: bias[M] is indexed by the ROW; col_rpb > 0: column n lies in
@@ -97,21 +88,6 @@ struct GemmArgs {
   int qn_H, qn_S, qn_s0, qn_dmodel;
   float qn_qscale;
 };
-
-// operands of the problem that tile row m0 belongs to (PAIR launches), as a GemmArgs the ordinary epilogue can take
-template <bool PAIR>
-__device__ __forceinline__ GemmArgs seg_args(const GemmArgs& g, long& m0) {
-  if (!PAIR || g.m_split == 0 || m0 < g.m_split) {
-    GemmArgs r = g;
-    if (PAIR && g.m_split) r.M = g.m_split;
-    return r;
-  }
-  GemmArgs r = g;
-  r.C = g.C2; r.c = g.c2; r.bias = g.bias2; r.gate = g.gate2; r.aux = g.aux2;
-  r.M = g.M - g.m_split;
-  m0 -= g.m_split;
-  return r;
-}
 
 // element offset of K-tile kt inside an A row
 template <bool CONV>
@@ -145,6 +121,55 @@ __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >>
 // anti-lever; the two waves of a SIMD run their epilogues beside each other's MFMA sections)
 __device__ __forceinline__ float vfma1(float sa /* wave-uniform */, float b, float c) { float r; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "s"(sa), "v"(b), "v"(c)); return r; }
 
+// Finishes 4 consecutive features n .. n + 3 of row m (C row offset crow, batch bidx) from their fp32 sums `a`, 8 bytes per
+// access: the epilogue of the 128x128 kernel, and the persistent kernel's where a side operand is not 16-byte addressable.
+// A macro, not a function: with a call in its place, inlined or not, hipcc lays out and register-allocates the persistent
+// kernels' 16-byte path (and the 128x128 kernel's GELU and gate forms) differently from the build whose measurements DESIGN.md
+// quotes; expanded in place both kernels keep their instruction streams.
+#define GEMM_EPILOGUE4(EPI, g, a, m, n, crow, bidx)                                                                      \
+  do {                                                                                                                   \
+    float v[4] = {(a)[0], (a)[1], (a)[2], (a)[3]};                                                                       \
+    if (EPI == EPI_F32_ACC) {                                                                                            \
+      float4* cp = reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + (crow) + (n));                              \
+      float4 o = make_float4(v[0], v[1], v[2], v[3]);                                                                    \
+      if (g.beta != 0.f) {                                                                                               \
+        const float4 old = *cp;                                                                                          \
+        o.x += g.beta * old.x; o.y += g.beta * old.y; o.z += g.beta * old.z; o.w += g.beta * old.w;                      \
+      }                                                                                                                  \
+      *cp = o;                                                                                                           \
+      break;                                                                                                             \
+    }                                                                                                                    \
+    if (g.bias) {                                                                                                        \
+      const uint2 bb = *reinterpret_cast<const uint2*>(g.bias + (n));                                                    \
+      v[0] += bf2f(bb.x & 0xffff); v[1] += bf2f(bb.x >> 16); v[2] += bf2f(bb.y & 0xffff); v[3] += bf2f(bb.y >> 16);      \
+    }                                                                                                                    \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) v[r] = rbf(v[r]);   /* the Linear's bf16 output */                    \
+    bf16_raw* cp = reinterpret_cast<bf16_raw*>(g.C) + (crow) + (n);                                                      \
+    uint2 pre;   /* kept for the backward pass: the pre-activation / the pre-gate branch output (for d(gate)) */        \
+    pre.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);                                                         \
+    pre.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);                                                         \
+    if (EPI == EPI_BIAS_GELU) {                                                                                          \
+      if (g.aux) *reinterpret_cast<uint2*>(g.aux + (m) * g.ldaux + (n)) = pre;                                           \
+      _Pragma("unroll") for (int r = 0; r < 4; ++r) v[r] = gelu_tanh_f(v[r]);                                            \
+    } else if (EPI == EPI_BIAS_GATE_RES) {                                                                               \
+      if (g.aux) *reinterpret_cast<uint2*>(g.aux + (m) * g.ldaux + (n)) = pre;                                           \
+      const uint2 gg = *reinterpret_cast<const uint2*>(g.gate + (bidx) * g.gate_ld + (n));                               \
+      const uint2 rr = *reinterpret_cast<const uint2*>(cp);                                                              \
+      v[0] = bf2f(rr.x & 0xffff) + rbf(bf2f(gg.x & 0xffff) * v[0]);                                                      \
+      v[1] = bf2f(rr.x >> 16) + rbf(bf2f(gg.x >> 16) * v[1]);                                                            \
+      v[2] = bf2f(rr.y & 0xffff) + rbf(bf2f(gg.y & 0xffff) * v[2]);                                                      \
+      v[3] = bf2f(rr.y >> 16) + rbf(bf2f(gg.y >> 16) * v[3]);                                                            \
+    } else if (EPI == EPI_BIAS_MULAUX) {   /* dgrad through GELU: C = (A@W^T) * gelu'(aux), aux = saved pre-activation */ \
+      const uint2 pp = *reinterpret_cast<const uint2*>(g.aux + (m) * g.ldaux + (n));                                     \
+      v[0] *= gelu_tanh_grad_f(bf2f(pp.x & 0xffff)); v[1] *= gelu_tanh_grad_f(bf2f(pp.x >> 16));                         \
+      v[2] *= gelu_tanh_grad_f(bf2f(pp.y & 0xffff)); v[3] *= gelu_tanh_grad_f(bf2f(pp.y >> 16));                         \
+    }                                                                                                                    \
+    uint2 o;                                                                                                             \
+    o.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);                                                           \
+    o.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);                                                           \
+    *reinterpret_cast<uint2*>(cp) = o;                                                                                   \
+  } while (0)
+
 // Epilogue of the 128x128 kernel: lane holds, for m-tile j and n-tile i, 4 consecutive features of one token.
 template <int EPI, int MT, int NTL>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[NTL][MT], int lane, long m0, long n0, int wm,
@@ -161,56 +186,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x4 (&acc)[NT
     for (int i = 0; i < NTL; ++i) {
       const long n = n0 + wn * 64 + i * 16 + fq * 4;
       if (n >= g.N) continue;   // N is a multiple of 4 (checked on the host)
-      float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      if (EPI == EPI_F32_ACC) {
-        float4* cp = reinterpret_cast<float4*>(reinterpret_cast<float*>(g.C) + crow + n);
-        float4 o = make_float4(v[0], v[1], v[2], v[3]);
-        if (g.beta != 0.f) {
-          const float4 old = *cp;
-          o.x += g.beta * old.x; o.y += g.beta * old.y; o.z += g.beta * old.z; o.w += g.beta * old.w;
-        }
-        *cp = o;
-        continue;
-      }
-      if (g.bias) {
-        const uint2 bb = *reinterpret_cast<const uint2*>(g.bias + n);
-        v[0] += bf2f(bb.x & 0xffff); v[1] += bf2f(bb.x >> 16); v[2] += bf2f(bb.y & 0xffff); v[3] += bf2f(bb.y >> 16);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = rbf(v[r]);   // the Linear's bf16 output
-      bf16_raw* cp = reinterpret_cast<bf16_raw*>(g.C) + crow + n;
-      if (EPI == EPI_BIAS_GELU) {
-        if (g.aux) {  // keep the pre-activation for the backward pass
-          uint2 pre;
-          pre.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-          pre.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-          *reinterpret_cast<uint2*>(g.aux + m * g.ldaux + n) = pre;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = gelu_tanh_f(v[r]);
-      } else if (EPI == EPI_BIAS_GATE_RES) {
-        if (g.aux) {  // pre-gate branch output, needed for d(gate)
-          uint2 pre;
-          pre.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-          pre.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-          *reinterpret_cast<uint2*>(g.aux + m * g.ldaux + n) = pre;
-        }
-        const uint2 gg = *reinterpret_cast<const uint2*>(g.gate + bidx * g.gate_ld + n);
-        const uint2 rr = *reinterpret_cast<const uint2*>(cp);
-        v[0] = bf2f(rr.x & 0xffff) + rbf(bf2f(gg.x & 0xffff) * v[0]);
-        v[1] = bf2f(rr.x >> 16) + rbf(bf2f(gg.x >> 16) * v[1]);
-        v[2] = bf2f(rr.y & 0xffff) + rbf(bf2f(gg.y & 0xffff) * v[2]);
-        v[3] = bf2f(rr.y >> 16) + rbf(bf2f(gg.y >> 16) * v[3]);
-      } else if (EPI == EPI_BIAS_MULAUX) {
-        // dgrad through GELU: C = (A@W^T) * gelu'(aux)   (aux = saved pre-activation)
-        const uint2 pp = *reinterpret_cast<const uint2*>(g.aux + m * g.ldaux + n);
-        v[0] *= gelu_tanh_grad_f(bf2f(pp.x & 0xffff)); v[1] *= gelu_tanh_grad_f(bf2f(pp.x >> 16));
-        v[2] *= gelu_tanh_grad_f(bf2f(pp.y & 0xffff)); v[3] *= gelu_tanh_grad_f(bf2f(pp.y >> 16));
-      }
-      uint2 o;
-      o.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-      o.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-      *reinterpret_cast<uint2*>(cp) = o;
+      GEMM_EPILOGUE4(EPI, g, acc[i][j], m, n, crow, bidx);
     }
   }
 }
@@ -230,20 +206,10 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmArgs g) {
   // XCD-aware tile order: consecutive logical tiles (which share A/W panels) go to the same XCD
   const int tiles_m = (g.M + TM - 1) / TM, tiles_n = (g.N + TN - 1) / TN;
   const int nwg = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  // walk N fastest inside a band of 8 M-tiles so a wave of tiles reuses the same W panels and A panels
-  const int band = 8;
-  const int per_band = band * tiles_n;
-  const int b0 = bid / per_band;
-  const int rows_in_band = min(band, tiles_m - b0 * band);
-  const int in_band = bid - b0 * per_band;
-  const int tm = b0 * band + in_band % rows_in_band;
-  const int tn = in_band / rows_in_band;
-  const long m0 = (long)tm * TM, n0 = (long)tn * TN;
+  const int blk = blockIdx.x, bid = gemm_plan::xcd_range(nwg, blk & 7).beg + (blk >> 3);
+  // bands of 8 tile rows, column-major inside a band: a wave of tiles reuses the same W panels and A panels
+  long m0, n0;
+  gemm_plan::tile_origin(bid, gemm_plan::SMALL_BAND, tiles_m, tiles_n, TM, TN, m0, n0);
 
   // ---- loader: thread owns 16-byte chunks (row = lrow + RS*i, kc = lkc), i = 0..3; RS*i leaves bits 1..3 of the row
   // alone, so the swizzle term is the same for all four and one LDS offset (+ RS*128*i) serves them
@@ -451,19 +417,17 @@ __global__ void __launch_bounds__(256) colsum_finish_kernel(const float* __restr
 // idle LDS buffer during the last K-step of the current one (no exposed prologue, no dispatch gap between tiles) and
 // the epilogue's global stores drain underneath the next tile's K-loop.
 //
-// Output layout trick: the W rows of each 64-row wave group are stored in LDS in the order
-//     LDS row t*16 + f  <-  W row (f>>2)*16 + t*4 + (f&3)            (the DMA source address is per lane: free)
-// so the accumulators acc[t = 0..3][j] of lane (fr, fq) are 16 CONSECUTIVE output features fq*16 + t*4 + r of token
-// row j*16 + fr: the epilogue runs straight from registers with 16-byte accesses (4 lanes = one 128-byte line per
-// row), with no LDS transpose, no bf16 round trip and no barrier before the next tile.
+// Output layout trick: the W rows of each 64-row wave group are stored in LDS permuted (`wperm`; the DMA source address is per
+// lane: free) so that the accumulators acc[t = 0..3][j] of lane (fr, fq) are, for token row j*16 + fr, output features
+// fq*8 .. fq*8+7 (t = 0, 1) and the same + 32 (t = 2, 3) of the wave's 64 (`lane_feat`): the epilogue runs straight from
+// registers with 16-byte accesses, with no LDS transpose, no bf16 round trip and no barrier before the next tile, and ONE
+// 16-byte store instruction of the wave writes 64 contiguous bytes per token row -- half a 128-byte line (16 consecutive
+// features per lane gave four 16-byte pieces 32 bytes apart: profiles/r02_ab_gemm_variants.log).
 //
 // Everything the epilogue reads from memory is requested UNCONDITIONALLY (clamped addresses) and in batches: a
 // per-row `if (in range) { load; use; store }` makes hipcc emit branch + load + s_waitcnt vmcnt(0) per row, i.e.
 // serial HBM round trips (vmcnt counts stores too, so each wait also drains the previous row's store): that form
 // cost ~20 us of an 80 us K=3072 tile.
-// (The lane's four accumulator tiles: t = 0, 1 are features fq*8 .. fq*8+7 and tiles t = 2, 3 the same + 32, so that ONE 16-byte store instruction of the wave
-// writes 64 contiguous bytes per token row -- half a 128-byte line -- instead of four 16-byte pieces 32 bytes apart, which is
-// what 16 CONSECUTIVE features per lane gave: profiles/r02_ab_gemm_variants.log.)
 __device__ __forceinline__ int wperm(int p) { return (p >> 5) * 32 + ((p & 15) >> 2) * 8 + ((p >> 4) & 1) * 4 + (p & 3); }
 __device__ __forceinline__ int lane_feat(int fq, int t) { return (t >> 1) * 32 + fq * 8 + (t & 1) * 4; }
 
@@ -735,38 +699,7 @@ __device__ __forceinline__ void persist_epilogue(const GemmArgs& g, f32x4 (&acc)
       for (int t = 0; t < 4; ++t) {
         const long nn = nw + lane_feat(fq, t);
         if (nn >= g.N) continue;
-        float v[4] = {acc[t][j][0], acc[t][j][1], acc[t][j][2], acc[t][j][3]};
-        if (g.bias) {
-          const uint2 bb = *reinterpret_cast<const uint2*>(g.bias + nn);
-          v[0] += bf2f(bb.x & 0xffff); v[1] += bf2f(bb.x >> 16); v[2] += bf2f(bb.y & 0xffff); v[3] += bf2f(bb.y >> 16);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = rbf(v[r]);
-        bf16_raw* cp = reinterpret_cast<bf16_raw*>(g.C) + crow + nn;
-        uint2 pre;
-        pre.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-        pre.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-        if (EPI == EPI_BIAS_GELU) {
-          if (g.aux) *reinterpret_cast<uint2*>(g.aux + m * g.ldaux + nn) = pre;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = gelu_tanh_f(v[r]);
-        } else if (EPI == EPI_BIAS_GATE_RES) {
-          if (g.aux) *reinterpret_cast<uint2*>(g.aux + m * g.ldaux + nn) = pre;
-          const uint2 gg = *reinterpret_cast<const uint2*>(g.gate + bidx * g.gate_ld + nn);
-          const uint2 rr = *reinterpret_cast<const uint2*>(cp);
-          v[0] = bf2f(rr.x & 0xffff) + rbf(bf2f(gg.x & 0xffff) * v[0]);
-          v[1] = bf2f(rr.x >> 16) + rbf(bf2f(gg.x >> 16) * v[1]);
-          v[2] = bf2f(rr.y & 0xffff) + rbf(bf2f(gg.y & 0xffff) * v[2]);
-          v[3] = bf2f(rr.y >> 16) + rbf(bf2f(gg.y >> 16) * v[3]);
-        } else if (EPI == EPI_BIAS_MULAUX) {
-          const uint2 pp = *reinterpret_cast<const uint2*>(g.aux + m * g.ldaux + nn);
-          v[0] *= gelu_tanh_grad_f(bf2f(pp.x & 0xffff)); v[1] *= gelu_tanh_grad_f(bf2f(pp.x >> 16));
-          v[2] *= gelu_tanh_grad_f(bf2f(pp.y & 0xffff)); v[3] *= gelu_tanh_grad_f(bf2f(pp.y >> 16));
-        }
-        uint2 o;
-        o.x = (uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16);
-        o.y = (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16);
-        *reinterpret_cast<uint2*>(cp) = o;
+        GEMM_EPILOGUE4(EPI, g, acc[t][j], m, nn, crow, bidx);
       }
     }
     return;
@@ -931,7 +864,7 @@ __device__ __forceinline__ void persist_epilogue(const GemmArgs& g, f32x4 (&acc)
 // rounds (the 3072 x 12288 weight gradients), 0.56 (3072 x 3072), 0.375 / 0.75 (the text stream), 3.375 / 4.2 (N = 3072 at
 // micro-batch 4 / 5): 0.55 s of a 13.1 s GEMM family (profiles/r03_gemm_shapes.jsonl).  So the LAST, partial round of every XCD
 // is shared out along K, IN LOCKSTEP: with R tiles left for the XCD's nw workgroups, every tile's K range is cut into
-// P = nw / R equal parts (2 <= P <= SK_PMAX) and workgroup w = p R + r runs part p of tile r -- the R workgroups of a part walk
+// P = nw / R equal parts (2 <= P <= 8) and workgroup w = p R + r runs part p of tile r -- the R workgroups of a part walk
 // the same K-tiles at the same time, so they share their A / W panels in the XCD's L2 exactly as the workgroups of a whole
 // round do (a first version dealt contiguous runs of tile slices, every workgroup at its own K offset: nothing was shared, the
 // tail ran at the fabric's bandwidth and returned a third of what the K-loop arithmetic promised; profiles/r04_gemm_sk_ab_contiguous_runs.log vs r04_gemm_sk_ab_lockstep.log).
@@ -939,61 +872,23 @@ __device__ __forceinline__ void persist_epilogue(const GemmArgs& g, f32x4 (&acc)
 // IN K ORDER and runs the ordinary epilogue: deterministic (no atomics, no flags, no spinning), and a given shape is always
 // split the same way, so the training forward and its recompute stay bit-identical.  What a split buys is (1 - 1 / P) of a
 // tile's K-loop, what it costs is the workspace round trip and the fix-up launch; launch() only allows it when the former is
-// clearly larger (sk_minparts).
-constexpr int SK_PMAX = 8;
+// clearly larger (gemm_plan::sk_minparts).  The dealing itself: gemm_plan::walk / fixup.
 constexpr long SK_SLOT = 256L * 256;      // floats per workspace slot
 
-__host__ __device__ inline int sk_parts(int R, int nw) { return R > 0 ? (nw / R < SK_PMAX ? nw / R : SK_PMAX) : 0; }
-__host__ __device__ inline bool sk_on(const float* ws, int minparts, int R, int nw, int nkt) {
-  const int P = sk_parts(R, nw);
-  return ws != nullptr && P >= 2 && P >= minparts && nkt >= 4 * P;
-}
-
-struct SkTail {
-  int nfull;               // whole tiles of this workgroup (rounds before the tail)
-  int nseg;                // tail units: 0 or 1
-  int tile0, k00, k01, part0;
-  int tile1, k11;          // (a second tail unit: unused by the lockstep dealing, kept for the unit walk's generality)
-};
-
-__device__ __forceinline__ SkTail sk_tail(const GemmArgs& g, int xcnt, int nw, int w, int nkt) {
-  SkTail t;
-  t.nfull = xcnt / nw;
-  const int R = xcnt - t.nfull * nw, base = t.nfull * nw;
-  t.nseg = 0; t.tile0 = 0; t.k00 = 0; t.k01 = nkt; t.part0 = 0; t.tile1 = 0; t.k11 = nkt;
-  if (!sk_on(g.sk_ws, g.sk_minparts, R, nw, nkt)) {
-    if (w < R) { t.nseg = 1; t.tile0 = base + w; }
-    return t;
-  }
-  const int P = sk_parts(R, nw);
-  if (w >= P * R) return t;
-  const int p = w / R, r = w - p * R;
-  t.nseg = 1; t.tile0 = base + r;
-  t.k00 = p * nkt / P; t.k01 = (p + 1) * nkt / P;
-  t.part0 = 1;
-  return t;
-}
-
-// One wave per (tail tile, wave slot of the main kernel): blockIdx.x = (r * 8 + xcd) * 8 + wid.  Mirrors gemm_pp_kernel's
-// tile walk and sk_tail()'s dealing.
-template <int EPI, bool PAIR>
+// One wave per (tail tile, wave slot of the main kernel): blockIdx.x = (r * 8 + xcd) * 8 + wid (gemm_plan::fixup).
+template <int EPI>
 __global__ void __launch_bounds__(64) gemm_sk_fixup_kernel(GemmArgs g, int nw) {
-  const int lane = threadIdx.x, wid = blockIdx.x & 7, xcd = (blockIdx.x >> 3) & 7, r = blockIdx.x >> 6;
-  const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + 255) / 256, nwg = tiles_m * tiles_n, nkt = g.K / BK;
-  const int q = nwg >> 3, rem = nwg & 7;
-  const int xbeg = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-  const int xcnt = xcd < rem ? q + 1 : q;
-  const int nfull = xcnt / nw, R = xcnt - nfull * nw;
-  if (r >= R || !sk_on(g.sk_ws, g.sk_minparts, R, nw, nkt)) return;
-  const int P = sk_parts(R, nw);
+  const int lane = threadIdx.x, wid = blockIdx.x & 7;
+  const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + 255) / 256;
+  const gemm_plan::Fixup f = gemm_plan::fixup(tiles_m * tiles_n, blockIdx.x, nw, g.sk_minparts, g.K / BK);
+  if (f.parts == 0) return;
   f32x4 acc[4][8];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int p = 0; p < P; ++p) {                    // ascending p = ascending K
-    const int w = p * R + r;
-    const float* wsp = g.sk_ws + ((long)(w * 8 + xcd) << 16) + ((wid * 32) * 64 + lane) * 4;
+  for (int p = 0; p < f.parts; ++p) {              // ascending p = ascending K
+    const float* wsp = g.sk_ws + ((long)(f.slot0 + p * f.stride) << 16) + ((wid * 32) * 64 + lane) * 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1002,13 +897,9 @@ __global__ void __launch_bounds__(64) gemm_sk_fixup_kernel(GemmArgs g, int nw) {
         acc[i][j] += v;
       }
   }
-  const int tl = xbeg + nfull * nw + r, band = g.band;
-  const int per_band = band * tiles_n, b0 = tl / per_band, rows_in_band = min(band, tiles_m - b0 * band);
-  const int in_band = tl - b0 * per_band;
-  long m0 = (long)(b0 * band + in_band % rows_in_band) * 256;
-  const long n0 = (long)(in_band / rows_in_band) * 256;
-  const GemmArgs gl = seg_args<PAIR>(g, m0);
-  if constexpr (EPI != EPI_QKNORM && EPI != EPI_QKNORM_P) persist_epilogue<EPI>(gl, acc, wid, lane, m0, n0);   // (QKNORM launches never split: launch())
+  long m0, n0;
+  gemm_plan::tile_origin(f.tile, g.band, tiles_m, tiles_n, 256, 256, m0, n0);
+  persist_epilogue<EPI>(g, acc, wid, lane, m0, n0);
 }
 
 // ------------------------------------------------------------------------------------------ persistent ping-pong kernel
@@ -1016,9 +907,7 @@ __global__ void __launch_bounds__(64) gemm_sk_fixup_kernel(GemmArgs g, int nw) {
 // TWO for W, filled by LDS-DMA (global_load_lds_dwordx4, XOR-swizzled through the per-lane SOURCE address) two K-tiles ahead;
 // raw s_barrier + counted vmcnt (__syncthreads() would drain the DMA queue); the pipeline runs on across output tiles.
 // Tile order: bands of `band` tile rows, column-major inside a band, so the 32 CUs of an XCD work on band x (32 / band) tiles
-// that share `band` A panels and 32 / band W panels.  The activation operand streams from HBM, the weights sit in the
-// Infinity Cache: narrow outputs (<= 16 tile columns) take band 1 -- a round is whole tile rows, every A panel is fetched
-// once -- wider ones band 4; few tile ROWS (wgrad shapes with 3072 output rows): one band of all rows, every W panel once.
+// that share `band` A panels and 32 / band W panels (gemm_plan::tile_origin; the band: gemm_plan::band_of).
 // (Round 1's K-loop -- all eight waves in the same phase -- is kept as text in scratch/gemm_persist_kernel_round1.hip.txt.)
 // The K-loop: a K-tile is TWO phases of 32 MFMAs per wave, each phase = [load section | barrier | MFMA section | barrier], and the second half of the waves
 // (wm = 1: the SIMD partners of the first half) runs ONE barrier behind, so that on every SIMD one wave's MFMA section
@@ -1036,9 +925,8 @@ __global__ void __launch_bounds__(64) gemm_sk_fixup_kernel(GemmArgs g, int nw) {
 // against the matrix pipe's 2048 (83-85 % busy) at a clock the chip holds at 1.71-1.76 GHz under this load; the first
 // version of this loop with FOUR phases of 16 MFMAs (8 barriers per K-tile) ran 2622-2703 cycles at 1.82-1.87 GHz and
 // 2.5-6 % fewer TFLOP/s (profiles/r02_gemm_pp4_ab.log), round 1's lockstep K-loop 6-8 % fewer (profiles/r02_gemm_pp_ab.log).
-template <int EPI, bool CONV, int MODE>
+template <int EPI, bool CONV, bool SK>
 __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
-  constexpr bool SK = (MODE & 1) != 0, PAIR = (MODE & 2) != 0;
   constexpr int TM = 256, TN = 256, NTHR = 512, RS = NTHR / 8, TB = TM * 128, MT = 8, NTL = 4;
   constexpr int WBASE = 3 * TB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1048,23 +936,16 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
   const int tiles_m = (g.M + TM - 1) / TM, tiles_n = (g.N + TN - 1) / TN;
   const int nwg = tiles_m * tiles_n;
   const int nkt = g.K / BK;
-  const int band = g.band;                // = tiles_n <= 16 ? 1 : (tiles_m <= 16 ? tiles_m : 4), launch()
+  const int band = g.band;                // gemm_plan::band_of, launch()
   const int xcd = blockIdx.x & 7, lane_in_xcd = blockIdx.x >> 3, per_xcd_wg = gridDim.x >> 3;
-  const int q = nwg >> 3, rem = nwg & 7;
-  const int xbeg = xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q;
-  const int xcnt = xcd < rem ? q + 1 : q;
+  const gemm_plan::XcdRange xr = gemm_plan::xcd_range(nwg, xcd);
+  const int xbeg = xr.beg;
   // ---- the workgroup's list of work units: `nfull` whole tiles (xbeg + lane_in_xcd + i * per_xcd_wg), then -- stream-K tail --
-  // up to two SEGMENTS (tile, K-tile range) of the XCD's last, partial round (SkTail)
+  // at most one part (tile, K-tile range) of the XCD's last, partial round (gemm_plan::walk)
   // (SK = false, every launch that splits nothing: the list is the strided tile walk and all of this folds away -- the unit
   //  bookkeeping costs the big rollout shapes ~1 %, profiles/r04_gemm_ab_r03_r04_a.log, so they do not carry it)
-  SkTail sk;
-  if (SK) {
-    sk = sk_tail(g, xcnt, per_xcd_wg, lane_in_xcd, nkt);
-  } else {
-    sk.nfull = lane_in_xcd < xcnt ? (xcnt - lane_in_xcd + per_xcd_wg - 1) / per_xcd_wg : 0;
-    sk.nseg = 0; sk.tile0 = 0; sk.k00 = 0; sk.k01 = nkt; sk.part0 = 0; sk.tile1 = 0; sk.k11 = nkt;
-  }
-  const int nunits = sk.nfull + sk.nseg;
+  const gemm_plan::Walk sk = gemm_plan::walk(SK, g.sk_minparts, xr.cnt, per_xcd_wg, lane_in_xcd, nkt);
+  const int nunits = sk.nfull + sk.ntail;
   if (nunits == 0) return;
   const int wu = __builtin_amdgcn_readfirstlane(wid);
   const bool late = wu >= 4;
@@ -1075,27 +956,16 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
   typedef const __attribute__((address_space(1))) char gbl_char;
   uint32_t ao[4], wo[4];
   long m0, n0;
-#define TILE_COORDS(tl, M0, N0)                                            \
-  do {                                                                     \
-    const int per_band = band * tiles_n;                                   \
-    const int b0 = (tl) / per_band;                                        \
-    const int rows_in_band = min(band, tiles_m - b0 * band);               \
-    const int in_band = (tl) - b0 * per_band;                              \
-    M0 = (long)(b0 * band + in_band % rows_in_band) * TM;                  \
-    N0 = (long)(in_band / rows_in_band) * TN;                              \
-  } while (0)
+#define TILE_COORDS(tl, M0, N0) GEMM_PLAN_TILE_ORIGIN(tl, band, tiles_m, tiles_n, TM, TN, M0, N0)
 #define TILE_OFFS(M0, N0, AO, WO)                                                          \
   do {                                                                                     \
     _Pragma("unroll") for (int k_ = 0; k_ < 4; ++k_) {                                     \
       long mm = M0 + lrow + k_ * RS;                                                       \
       if (mm >= g.M) mm = g.M - 1;                                                         \
-      const bool s2_ = PAIR && g.m_split && M0 >= g.m_split;                               \
-      const long ar_ = !PAIR ? row_off(g.a, mm)                                            \
-                             : (s2_ ? row_off(g.a2, mm - g.m_split) + g.a2_off : row_off(g.a, mm) + g.a1_off); \
-      AO[k_] = (uint32_t)((ar_ + src_kc * 8) * 2);                                         \
+      AO[k_] = (uint32_t)((row_off(g.a, mm) + src_kc * 8) * 2);                            \
       long nn = N0 + k_ * 64 + wrow;                                                       \
       if (nn >= g.N) nn = g.N - 1;                                                         \
-      WO[k_] = (uint32_t)((nn * g.ldw + (!PAIR ? 0 : (s2_ ? g.w2_off : g.w1_off)) + src_kc * 8) * 2); \
+      WO[k_] = (uint32_t)((nn * g.ldw + src_kc * 8) * 2);                                  \
     }                                                                                      \
   } while (0)
 #define PGLDS(base, off, off_lds) \
@@ -1113,17 +983,11 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
 #define LDW(ks, i) (*reinterpret_cast<const s16x8*>(smem + sw_ + w_ro[ks] + (i) * 2048))
 #define MMA(i_, j_, W_, A_) acc[i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(W_, A_, acc[i_][j_], 0, 0, 0)
 
-#define PGLDS_K PGLDS
-#define LDA_K LDA
-#define LDW_K LDW
   // unit i of this workgroup -> (tile index inside the XCD's range, K-tile range, partial?)
-#define UNIT(i, T_, K0_, K1_, P_)                                                        \
-  do {                                                                                     \
-    const int s_ = SK ? (i) - sk.nfull : -1;                                               \
-    T_ = s_ < 0 ? lane_in_xcd + (i) * per_xcd_wg : (s_ == 0 ? sk.tile0 : sk.tile1);       \
-    K0_ = s_ < 0 ? 0 : (s_ == 0 ? sk.k00 : 0);                                             \
-    K1_ = s_ < 0 ? nkt : (s_ == 0 ? sk.k01 : sk.k11);                                      \
-    P_ = s_ < 0 ? 0 : (s_ == 0 ? sk.part0 : 1);                                            \
+#define UNIT(i, T_, K0_, K1_, P_)                                                                  \
+  do {                                                                                             \
+    const gemm_plan::Unit u_ = gemm_plan::unit(SK, sk, (i), lane_in_xcd, per_xcd_wg, nkt);         \
+    T_ = u_.tile; K0_ = u_.k0; K1_ = u_.k1; P_ = u_.partial;                                       \
   } while (0)
   int ui = 0, u_tile, kbeg, kend, partial;
   UNIT(0, u_tile, kbeg, kend, partial);
@@ -1162,7 +1026,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
     for (int i = 0; i < NTL; ++i)
 #pragma unroll
       for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int klen = kend - kbeg;                   // >= 2 (sk_tail)
+    const int klen = kend - kbeg;                   // >= 2 (gemm_plan::sk_on)
     for (int kt = 0; kt < klen; ++kt) {
       const bool nxt = kt + 2 >= klen;
       const int k2 = nxt ? nkbeg + (kt + 2 - klen) : kbeg + kt + 2;
@@ -1181,13 +1045,13 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fw[ks][i] = LDW_K(ks, i);
+        for (int i = 0; i < 4; ++i) fw[ks][i] = LDW(ks, i);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) faA[ks][j] = LDA_K(ks, j);
+        for (int j = 0; j < 4; ++j) faA[ks][j] = LDA(ks, j);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) PGLDS_K(ab_, ca[k], la_ + k * RS * 128);
+      for (int k = 0; k < 4; ++k) PGLDS(ab_, ca[k], la_ + k * RS * 128);
       BAR();
       // ---- MA: tokens 0-63 x features 0-63
       __builtin_amdgcn_s_setprio(1);
@@ -1203,9 +1067,9 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) faB[ks][j] = LDA_K(ks, 4 + j);
+        for (int j = 0; j < 4; ++j) faB[ks][j] = LDA(ks, 4 + j);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) PGLDS_K(wb_, cw[k], lw_ + k * RS * 128);
+      for (int k = 0; k < 4; ++k) PGLDS(wb_, cw[k], lw_ + k * RS * 128);
       PIN();
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       BAR();
@@ -1234,10 +1098,6 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
       for (int i = 0; i < NTL; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j) *reinterpret_cast<f32x4*>(wsp + (i * MT + j) * 256) = acc[i][j];
-    } else if (PAIR) {
-      long m0l = m0;
-      const GemmArgs gl = seg_args<true>(g, m0l);
-      persist_epilogue<EPI>(gl, acc, ew, el, m0l, n0);
     } else {
       // (EPI_QKNORM: the A stage the next K-tile's DMA will fill -- its last readers, the late half's LB of this tile's last
       //  K-tile, are one barrier back for the early half and two for the late one)
@@ -1257,87 +1117,73 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
 #undef PGLDS
 #undef PIN
 #undef BAR
-#undef PGLDS_K
-#undef LDA_K
-#undef LDW_K
 #undef LDA
 #undef LDW
 #undef MMA
 }
 
-// what the persistent 256x256 kernel takes (the rest goes to gemm_kernel): enough tiles to fill most of the 256 CUs
-// (measured, scratch/bench_gemm_small.py: 168 tiles 843-935 vs 591-691 TFLOP/s, 120 tiles equal, 24-96 tiles slower)
-bool persistent_ok(const GemmArgs& g) {
-  const long tiles_big = (long)cdiv(g.M, 256) * cdiv(g.N, 256);
-  static const long min_tiles = getenv("MGX_GEMM_BIG_MIN_TILES") ? atol(getenv("MGX_GEMM_BIG_MIN_TILES")) : 128;
-  static const int mode = getenv("MGX_GEMM_MODE") ? atoi(getenv("MGX_GEMM_MODE")) : 9;     // 0 (debugging): 128x128 kernel everywhere
-  const bool big = g.M >= 256 && g.N >= 256 && tiles_big >= min_tiles && (g.N % 256 == 0 || g.N >= 2048);
-  return big && mode != 0 && g.span32 && g.K >= 2 * BK;
+// The MGX_GEMM_* variables, read once.  All of them are for A/B measurements and debugging.
+struct GemmEnv {
+  int mode;              // MGX_GEMM_MODE=0: the 128x128 kernel everywhere
+  int band;              // MGX_GEMM_BAND > 0: the persistent kernel's band, over the rule and any caller's hint
+  long big_min_tiles;    // MGX_GEMM_BIG_MIN_TILES: 256x256 tiles from which the persistent kernel runs
+  bool sk_off;           // MGX_GEMM_SK=0: no stream-K tail, workspace or not
+  float sk_cost_us;      // MGX_GEMM_SK_COST_US, MGX_GEMM_SK_SLOWDOWN: the constants of gemm_plan::sk_minparts
+  float sk_slow;
+  bool qknorm_off;       // MGX_GEMM_QKNORM=0: mgx_linear_qk_norm_rope declines everything
+};
+const GemmEnv& gemm_env() {
+  static const GemmEnv e = [] {
+    auto num = [](const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; };
+    GemmEnv r;
+    r.mode = (int)num("MGX_GEMM_MODE", 9);
+    r.band = (int)num("MGX_GEMM_BAND", 0);
+    r.big_min_tiles = (long)num("MGX_GEMM_BIG_MIN_TILES", gemm_plan::PP_MIN_TILES);
+    r.sk_off = (int)num("MGX_GEMM_SK", 1) == 0;
+    r.sk_cost_us = (float)num("MGX_GEMM_SK_COST_US", 40.);
+    r.sk_slow = (float)num("MGX_GEMM_SK_SLOWDOWN", 1.25);
+    r.qknorm_off = (int)num("MGX_GEMM_QKNORM", 1) == 0;
+    return r;
+  }();
+  return e;
 }
 
+// the persistent kernel takes the problem: its shape (gemm_plan::persistent_shape) and 32-bit DMA source offsets
+bool persistent_ok(int M, int N, int K, bool span32) {
+  const GemmEnv& e = gemm_env();
+  return gemm_plan::persistent_shape(M, N, K, e.big_min_tiles) && e.mode != 0 && span32;
+}
+// ... and how: band (`hint` > 0: the caller's) and launch
+int pp_band(int hint, int M, int N) { return gemm_plan::band_of(gemm_env().band > 0 ? gemm_env().band : hint, cdiv(M, 256), cdiv(N, 256)); }
+gemm_plan::PpLaunch pp_launch(int M, int N, int K, bool sk) {
+  const GemmEnv& e = gemm_env();
+  return gemm_plan::pp_launch(M, N, K, sk && !e.sk_off, e.sk_cost_us, e.sk_slow);
+}
+
+// Returns 1 -- nothing launched -- for an EPI_QKNORM problem the persistent kernel cannot take: its epilogue exists there only.
 template <int EPI, bool CONV = false>
 int launch(const GemmArgs& g_in, hipStream_t st) {
+  constexpr bool QKNORM = EPI == EPI_QKNORM || EPI == EPI_QKNORM_P;
   GemmArgs g = g_in;
-  {
-    const int tiles_m = cdiv(g.M, 256), tiles_n = cdiv(g.N, 256);
-    static const int band_env = getenv("MGX_GEMM_BAND") ? atoi(getenv("MGX_GEMM_BAND")) : 0;      // A/B only
-    g.band = band_env > 0 ? min(band_env, tiles_m) : (g.band > 0 ? min(g.band, tiles_m) : (tiles_n <= 16 ? 1 : (tiles_m <= 16 ? tiles_m : 4)));
-  }
-  const long tiles_big = (long)cdiv(g.M, 256) * cdiv(g.N, 256);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<EPI, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, CONV, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    if (!CONV) {
-      (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-      (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-      (void)hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-    }
-    attr_set = true;
-  }
-  const bool pair = !CONV && g.m_split != 0;
-  if (EPI == EPI_QKNORM || EPI == EPI_QKNORM_P) g.sk_ws = nullptr;     // its epilogue needs the whole workgroup: no split tiles
-  if (persistent_ok(g)) {
-    int grid = 256;                       // one workgroup per CU (multiple of 8: XCD ranges)
-    // stream-K tail (caller gave a workspace): allowed when it shortens the launch.  A tile's K-loop takes T ~ K * 0.0247 us
-    // (2 * 256 * 256 * K FLOP at the 5.3 TFLOP/s a CU sustains in this kernel).  Unsplit, the last round takes T; split P ways
-    // it takes T / P -- times a slowdown for the P-fold panel traffic of the tail (P parts x (rows + columns) panels per step
-    // against one round's) -- plus ~40 us for the workspace round trip and the fix-up launch:
-    //     split  <=>  T * (1 - slow / P) > cost.
-    static const float sk_cost_us = getenv("MGX_GEMM_SK_COST_US") ? (float)atof(getenv("MGX_GEMM_SK_COST_US")) : 40.f;
-    static const float sk_slow = getenv("MGX_GEMM_SK_SLOWDOWN") ? (float)atof(getenv("MGX_GEMM_SK_SLOWDOWN")) : 1.25f;
-    static const int sk_off = getenv("MGX_GEMM_SK") ? atoi(getenv("MGX_GEMM_SK")) == 0 : 0;
-    int rmax = 0;
-    g.sk_minparts = 0;
-    if (g.sk_ws && !sk_off && !CONV) {
-      const float tile_us = (float)g.K * 0.0247f;
-      const float room = 1.f - sk_cost_us / tile_us;                 // split <=> slow / P < room
-      g.sk_minparts = room <= 0.f ? SK_PMAX + 1 : (int)floorf(sk_slow / room) + 1;
-      if (g.sk_minparts < 2) g.sk_minparts = 2;
-      const int nw = grid / 8, q = (int)(tiles_big >> 3), rem = (int)(tiles_big & 7);
-      for (int x = 0; x < 8; ++x) {
-        const int cnt = x < rem ? q + 1 : q, R = cnt % nw;
-        if (sk_on(g.sk_ws, g.sk_minparts, R, nw, g.K / BK) && R > rmax) rmax = R;
-      }
-    }
-    if (rmax == 0) {
-      g.sk_ws = nullptr;
-      if (tiles_big < grid) grid = (int)((tiles_big + 7) / 8 * 8);
-    }
-    if (rmax > 0 && pair) {
-      gemm_pp_kernel<EPI, false, 3><<<grid, 512, 163840, st>>>(g);
-      gemm_sk_fixup_kernel<EPI, true><<<rmax * 64, 64, 0, st>>>(g, grid / 8);
-    } else if (rmax > 0) {
-      gemm_pp_kernel<EPI, false, 1><<<grid, 512, 163840, st>>>(g);
-      gemm_sk_fixup_kernel<EPI, false><<<rmax * 64, 64, 0, st>>>(g, grid / 8);
-    } else if (pair) {
-      gemm_pp_kernel<EPI, false, 2><<<grid, 512, 163840, st>>>(g);
-    } else {
-      gemm_pp_kernel<EPI, CONV, 0><<<grid, 512, 163840, st>>>(g);
-    }
+  g.band = pp_band(g.band, g.M, g.N);
+  g.sk_minparts = 0;
+  if (!persistent_ok(g.M, g.N, g.K, g.span32)) {
+    if constexpr (QKNORM) return 1;
+    else launch_lds<gemm_kernel<EPI, CONV>, 65536>(cdiv(g.M, BM) * cdiv(g.N, BN), NT, st, g);
+  } else if constexpr (QKNORM || CONV) {         // (QKNORM: its epilogue needs the whole workgroup: no split tiles)
+    g.sk_ws = nullptr;
+    launch_lds<gemm_pp_kernel<EPI, CONV, false>, 163840>(pp_launch(g.M, g.N, g.K, false).grid, 512, st, g);
   } else {
-    if (pair) return 1;                   // only the persistent kernel walks two problems: the caller launches them one by one
-    gemm_kernel<EPI, CONV><<<cdiv(g.M, BM) * cdiv(g.N, BN), NT, 65536, st>>>(g);
+    // stream-K tail (the caller gave a workspace): taken when it shortens the launch (gemm_plan::sk_minparts)
+    const gemm_plan::PpLaunch p = pp_launch(g.M, g.N, g.K, g.sk_ws != nullptr);
+    g.sk_minparts = p.sk_minparts;
+    if (p.sk_rmax > 0) {
+      launch_lds<gemm_pp_kernel<EPI, false, true>, 163840>(p.grid, 512, st, g);
+      gemm_sk_fixup_kernel<EPI><<<p.sk_rmax * 64, 64, 0, st>>>(g, p.grid / 8);
+    } else {
+      g.sk_ws = nullptr;
+      launch_lds<gemm_pp_kernel<EPI, false, false>, 163840>(p.grid, 512, st, g);
+    }
   }
   MGX_CHECK_LAUNCH();
   return MGX_OK;
@@ -1385,6 +1231,31 @@ bool side_ok16(int N, int M, const void* C, long ldc, long c_rpb, long c_bstride
          (!aux || (ldaux % 8 == 0 && (uintptr_t)aux % 16 == 0)) && (!gate || (gate_ld % 8 == 0 && (uintptr_t)gate % 16 == 0)) &&
          (!bias || (uintptr_t)bias % 16 == 0);
 }
+
+// The part of GemmArgs every entry point fills the same way: a plain GEMM (no convolution, no transposed output, no QK-norm)
+// on row-batched A (rows a) and C (rows c), with rows-per-batch clamped to 2^30 for the kernels' 32-bit divisions, the 16-byte
+// epilogue where every side operand allows it, and span32 from the last element either operand reaches.
+GemmArgs gemm_args(const uint16_t* A, const uint16_t* W, const uint16_t* bias, void* C, int M, int N, int K, RowMap a, RowMap c,
+                   long ldw, const uint16_t* gate = nullptr, long gate_ld = 0, uint16_t* aux = nullptr, long ldaux = 0) {
+  const long RPB_MAX = 1L << 30;
+  GemmArgs g{};
+  g.A = A; g.W = W; g.bias = bias; g.C = C; g.gate = gate; g.aux = aux; g.ldaux = ldaux; g.gate_ld = gate_ld;
+  g.M = M; g.N = N; g.K = K;
+  g.a = RowMap{a.ld, a.rpb < RPB_MAX ? a.rpb : RPB_MAX, a.bstride};
+  g.c = RowMap{c.ld, c.rpb < RPB_MAX ? c.rpb : RPB_MAX, c.bstride};
+  g.ldw = ldw;
+  g.conv_shift = -1;
+  g.rowwise_ok = side_ok16(N, M, C, c.ld, c.rpb, c.bstride, aux, ldaux, gate, gate_ld, bias);
+  const long a_last = (long)((M - 1) / a.rpb) * a.bstride + (long)((M - 1) % a.rpb) * a.ld + K;
+  g.span32 = a_last * 2 < (1L << 32) && ((long)N * ldw) * 2 < (1L << 32);
+  return g;
+}
+
+int check_sk_workspace(const float* sk_workspace, long sk_workspace_elems) {
+  MGX_REQUIRE(!sk_workspace || (sk_workspace_elems >= mgx_gemm_sk_workspace_elems() && (uintptr_t)sk_workspace % 16 == 0),
+              "stream-K workspace too small (mgx_gemm_sk_workspace_elems) or misaligned");
+  return MGX_OK;
+}
 }  // namespace
 
 extern "C" int mgx_gemm_bf16_sk(const uint16_t* A, const uint16_t* W, const uint16_t* bias, void* C, const uint16_t* gate,
@@ -1392,8 +1263,7 @@ extern "C" int mgx_gemm_bf16_sk(const uint16_t* A, const uint16_t* W, const uint
                                 long c_rpb, long c_bstride, long gate_ld, int epilogue, float beta, float* sk_workspace,
                                 long sk_workspace_elems, void* stream) {
   MGX_REQUIRE(A && W && C, "null operand");
-  MGX_REQUIRE(!sk_workspace || (sk_workspace_elems >= mgx_gemm_sk_workspace_elems() && (uintptr_t)sk_workspace % 16 == 0),
-              "stream-K workspace too small (mgx_gemm_sk_workspace_elems) or misaligned");
+  if (const int rc = check_sk_workspace(sk_workspace, sk_workspace_elems)) return rc;
   MGX_REQUIRE(M > 0 && N > 0 && K > 0, "empty GEMM");
   MGX_REQUIRE(K % BK == 0, "K must be a multiple of 64");
   MGX_REQUIRE(N % 4 == 0, "N must be a multiple of 4");
@@ -1404,82 +1274,11 @@ extern "C" int mgx_gemm_bf16_sk(const uint16_t* A, const uint16_t* W, const uint
   MGX_REQUIRE(((uintptr_t)A % 16 == 0) && ((uintptr_t)W % 16 == 0) && ((uintptr_t)C % 8 == 0), "operands must be 16-byte aligned");
   MGX_REQUIRE(epilogue != EPI_BIAS_GATE_RES || gate, "gate-residual epilogue needs a gate");
   MGX_REQUIRE(epilogue != EPI_BIAS_MULAUX || aux, "gelu-backward epilogue needs the saved pre-activation");
-  GemmArgs g{};
-  g.A = A; g.W = W; g.bias = bias; g.C = C; g.gate = gate; g.aux = aux; g.ldaux = ldaux; g.gate_ld = gate_ld;
-  g.M = M; g.N = N; g.K = K;
-  const long RPB_MAX = 1L << 30;
-  g.a = RowMap{lda, a_rpb < RPB_MAX ? a_rpb : RPB_MAX, a_bstride};
-  g.c = RowMap{ldc, c_rpb < RPB_MAX ? c_rpb : RPB_MAX, c_bstride};
-  g.ldw = ldw;
+  GemmArgs g = gemm_args(A, W, bias, C, M, N, K, RowMap{lda, a_rpb, a_bstride}, RowMap{ldc, c_rpb, c_bstride}, ldw, gate, gate_ld,
+                         aux, ldaux);
   g.beta = beta;
-  g.conv_shift = -1; g.conv_dy = 0; g.conv_dx = 0;
-  g.sk_ws = sk_workspace; g.sk_minparts = 0;
-  g.m_split = 0;
-  g.rowwise_ok = side_ok16(N, M, C, ldc, c_rpb, c_bstride, aux, ldaux, gate, gate_ld, bias);
-  {
-    const long a_last = (long)((M - 1) / a_rpb) * a_bstride + (long)((M - 1) % a_rpb) * lda + K;
-    g.span32 = a_last * 2 < (1L << 32) && ((long)N * ldw) * 2 < (1L << 32);
-  }
+  g.sk_ws = sk_workspace;
   return dispatch(g, epilogue, (hipStream_t)stream);
-}
-
-// Two problems of equal N, K, epilogue and leading dimensions in ONE launch of the persistent kernel: the text- and the
-// image-stream Linear of a FLUX double block (diffusers issues them as separate nn.Linear calls,
-// fastvideo/utils/sampling_utils.py:68-82).  The tile grid's first M1 rows are problem 1, the rest problem 2 (M1 % 256 == 0),
-// so the text stream's few tile rows ride the image stream's rounds instead of occupying a third of the chip for a tile time
-// of their own.  The second problem's A / W must lie within 4 GiB of the first's (the same activation buffer / the same block of
-// the parameter store).  Whatever the persistent kernel cannot take goes out as two launches of mgx_gemm_bf16_sk: same results.
-extern "C" int mgx_gemm_bf16_pair(const uint16_t* A1, const uint16_t* W1, const uint16_t* bias1, void* C1, const uint16_t* gate1,
-                                  uint16_t* aux1, int M1, long a1_rpb, long a1_bstride, long c1_rpb, long c1_bstride,
-                                  const uint16_t* A2, const uint16_t* W2, const uint16_t* bias2, void* C2, const uint16_t* gate2,
-                                  uint16_t* aux2, int M2, long a2_rpb, long a2_bstride, long c2_rpb, long c2_bstride, int N, int K,
-                                  long lda, long ldw, long ldc, long ldaux, long gate_ld, int epilogue, float beta,
-                                  float* sk_workspace, long sk_workspace_elems, void* stream) {
-  MGX_REQUIRE(A1 && W1 && C1 && A2 && W2 && C2, "null operand");
-  MGX_REQUIRE((bias1 == nullptr) == (bias2 == nullptr) && (gate1 == nullptr) == (gate2 == nullptr) && (aux1 == nullptr) == (aux2 == nullptr),
-              "the two problems must use the same optional operands");
-  const long RPB_MAX = 1L << 30;
-  // offsets are taken from the LOWER of the two pointers (the image stream's weights precede the text stream's in the store)
-  const uint16_t* Ab = A1 < A2 ? A1 : A2;
-  const uint16_t* Wb = W1 < W2 ? W1 : W2;
-  const long a1o = A1 - Ab, a2o = A2 - Ab, w1o = W1 - Wb, w2o = W2 - Wb;
-  bool groupable = M1 > 0 && M2 > 0 && M1 % 256 == 0 && epilogue != EPI_F32_ACC && K % BK == 0 && N % 4 == 0 &&
-                   ((uintptr_t)A1 % 16 == 0) && ((uintptr_t)W1 % 16 == 0) && ((uintptr_t)A2 % 16 == 0) && ((uintptr_t)W2 % 16 == 0) &&
-                   a2_rpb > 0 && c2_rpb > 0 && a1_rpb > 0 && c1_rpb > 0;
-  if (groupable) {
-    const long a1_last = a1o + (long)((M1 - 1) / a1_rpb) * a1_bstride + (long)((M1 - 1) % a1_rpb) * lda + K;
-    const long a2_last = a2o + (long)((M2 - 1) / a2_rpb) * a2_bstride + (long)((M2 - 1) % a2_rpb) * lda + K;
-    groupable = a1_last * 2 < (1L << 32) && a2_last * 2 < (1L << 32) && ((w1o > w2o ? w1o : w2o) + (long)N * ldw) * 2 < (1L << 32);
-  }
-  if (groupable) {
-    MGX_REQUIRE(!sk_workspace || (sk_workspace_elems >= mgx_gemm_sk_workspace_elems() && (uintptr_t)sk_workspace % 16 == 0),
-                "stream-K workspace too small (mgx_gemm_sk_workspace_elems) or misaligned");
-    MGX_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0 && (!aux1 || ldaux % 4 == 0), "leading dimensions must keep alignment");
-    MGX_REQUIRE(epilogue != EPI_BIAS_GATE_RES || gate1, "gate-residual epilogue needs a gate");
-    MGX_REQUIRE(epilogue != EPI_BIAS_MULAUX || aux1, "gelu-backward epilogue needs the saved pre-activation");
-    GemmArgs g{};
-    g.A = Ab; g.W = Wb; g.bias = bias1; g.C = C1; g.gate = gate1; g.aux = aux1; g.ldaux = ldaux; g.gate_ld = gate_ld;
-    g.M = M1 + M2; g.N = N; g.K = K;
-    g.a = RowMap{lda, a1_rpb < RPB_MAX ? a1_rpb : RPB_MAX, a1_bstride};
-    g.c = RowMap{ldc, c1_rpb < RPB_MAX ? c1_rpb : RPB_MAX, c1_bstride};
-    g.ldw = ldw; g.beta = beta;
-    g.conv_shift = -1; g.conv_dy = 0; g.conv_dx = 0;
-    g.sk_ws = sk_workspace; g.sk_minparts = 0;
-    g.m_split = M1; g.a1_off = a1o; g.a2_off = a2o; g.w1_off = w1o; g.w2_off = w2o;
-    g.a2 = RowMap{lda, a2_rpb < RPB_MAX ? a2_rpb : RPB_MAX, a2_bstride};
-    g.c2 = RowMap{ldc, c2_rpb < RPB_MAX ? c2_rpb : RPB_MAX, c2_bstride};
-    g.C2 = C2; g.bias2 = bias2; g.gate2 = gate2; g.aux2 = aux2;
-    g.rowwise_ok = side_ok16(N, M1, C1, ldc, c1_rpb, c1_bstride, aux1, ldaux, gate1, gate_ld, bias1) &&
-                   side_ok16(N, M2, C2, ldc, c2_rpb, c2_bstride, aux2, ldaux, gate2, gate_ld, bias2);
-    g.span32 = 1;
-    const int rc = dispatch(g, epilogue, (hipStream_t)stream);
-    if (rc <= 0) return rc;               // launched (0) or failed (< 0); 1: too small for the persistent kernel
-  }
-  const int rc = mgx_gemm_bf16_sk(A1, W1, bias1, C1, gate1, aux1, ldaux, M1, N, K, lda, a1_rpb, a1_bstride, ldw, ldc, c1_rpb, c1_bstride,
-                                  gate_ld, epilogue, beta, sk_workspace, sk_workspace_elems, stream);
-  if (rc) return rc;
-  return mgx_gemm_bf16_sk(A2, W2, bias2, C2, gate2, aux2, ldaux, M2, N, K, lda, a2_rpb, a2_bstride, ldw, ldc, c2_rpb, c2_bstride, gate_ld,
-                          epilogue, beta, sk_workspace, sk_workspace_elems, stream);
 }
 
 // Ct[b][f][t] = bf16(X[b * tok_rpb + t, :] . W[f, :] + bias[f]): a Linear whose output leaves TRANSPOSED, token-contiguous
@@ -1492,29 +1291,22 @@ extern "C" int mgx_linear_bf16_t(const uint16_t* X, const uint16_t* W, const uin
                                  long ldx, long ldw, long ld_ct, long tok_rpb, long ct_bstride, float* sk_workspace,
                                  long sk_workspace_elems, void* stream) {
   MGX_REQUIRE(X && W && Ct && tokens > 0 && F > 0 && K > 0 && tok_rpb > 0, "bad argument");
-  MGX_REQUIRE(!sk_workspace || (sk_workspace_elems >= mgx_gemm_sk_workspace_elems() && (uintptr_t)sk_workspace % 16 == 0),
-              "stream-K workspace too small (mgx_gemm_sk_workspace_elems) or misaligned");
+  if (const int rc = check_sk_workspace(sk_workspace, sk_workspace_elems)) return rc;
   const long rpb = tok_rpb < tokens ? tok_rpb : tokens;
   const long nb = (tokens + rpb - 1) / rpb;
   const bool ok = K % BK == 0 && tokens % 8 == 0 && F % 4 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ld_ct % 8 == 0 && ct_bstride % 8 == 0 &&
                   (nb == 1 || rpb % 64 == 0) && ld_ct >= rpb && ((uintptr_t)X % 16 == 0) && ((uintptr_t)W % 16 == 0) &&
                   ((uintptr_t)Ct % 16 == 0) && (!bias || (uintptr_t)bias % 2 == 0);
   if (!ok) return 1;
-  GemmArgs g{};
-  g.A = W; g.W = X; g.bias = bias; g.C = Ct;
-  g.M = F; g.N = tokens; g.K = K;
-  g.a = RowMap{ldw, 1L << 30, 0};
-  g.c = RowMap{ld_ct, 1L << 30, 0};
-  g.ldw = ldx;
-  g.conv_shift = -1;
+  GemmArgs g = gemm_args(W, X, bias, Ct, F, tokens, K, RowMap{ldw, 1L << 30, 0}, RowMap{ld_ct, 1L << 30, 0}, ldx);
   g.sk_ws = sk_workspace;
-  g.rowwise_ok = 1;
+  g.rowwise_ok = 1;                       // (`ok`; the bias is read per ROW, element by element: 2-byte alignment will do)
   g.bias_rows = 1;
   g.col_rpb = nb > 1 ? rpb : 0; g.col_bstride = ct_bstride;
   g.band = 6;     // (a caller's hint, launch(): bands of 6 feature-tile rows -- 0.522 ms against 0.534 ms for one band of all 12 at
                   //  3072 x 36864 x 3072, profiles/r04_split_projection_band_sweep.log; the weight gradients keep their rule)
   g.span32 = ((long)F * ldw) * 2 < (1L << 32) && ((long)tokens * ldx) * 2 < (1L << 32);
-  if (!persistent_ok(g)) return 1;
+  if (!persistent_ok(g.M, g.N, g.K, g.span32)) return 1;
   return launch<EPI_BIAS>(g, (hipStream_t)stream);
 }
 
@@ -1530,26 +1322,17 @@ extern "C" int mgx_linear_qk_norm_rope(const uint16_t* X, const uint16_t* Wqk, c
   MGX_REQUIRE(X && Wqk && wq && wk && cos && sin && Q && K, "null argument");
   MGX_REQUIRE(!cos_sin_pairs || (uintptr_t)cos_sin_pairs % 16 == 0, "pair table must be 16-byte aligned");
   MGX_REQUIRE(B > 0 && H > 0 && rows_per_batch > 0 && s0 >= 0 && s0 + rows_per_batch <= S && Kdim > 0 && q_scale > 0.f, "bad sizes");
-  static const int off = getenv("MGX_GEMM_QKNORM") ? atoi(getenv("MGX_GEMM_QKNORM")) == 0 : 0;
   const long tokens = (long)B * rows_per_batch;
   const int dmodel = H * 128;
-  const bool ok = !off && dmodel % 256 == 0 && rows_per_batch % 128 == 0 && Kdim % BK == 0 && ldx % 8 == 0 && ldw % 8 == 0 &&
-                  tokens < (1L << 31) && ((uintptr_t)X % 16 == 0) && ((uintptr_t)Wqk % 16 == 0) && ((uintptr_t)Q % 16 == 0) &&
-                  ((uintptr_t)K % 16 == 0) && ((uintptr_t)cos % 16 == 0) && ((uintptr_t)sin % 16 == 0) &&
+  const bool ok = !gemm_env().qknorm_off && dmodel % 256 == 0 && rows_per_batch % 128 == 0 && Kdim % BK == 0 && ldx % 8 == 0 &&
+                  ldw % 8 == 0 && tokens < (1L << 31) && ((uintptr_t)X % 16 == 0) && ((uintptr_t)Wqk % 16 == 0) &&
+                  ((uintptr_t)Q % 16 == 0) && ((uintptr_t)K % 16 == 0) && ((uintptr_t)cos % 16 == 0) && ((uintptr_t)sin % 16 == 0) &&
                   ((uintptr_t)wq % 16 == 0) && ((uintptr_t)wk % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0);
   if (!ok) return 1;
-  GemmArgs g{};
-  g.A = X; g.W = Wqk; g.bias = bias; g.C = Q;
-  g.M = (int)tokens; g.N = 2 * dmodel; g.K = Kdim;
-  g.a = RowMap{ldx, 1L << 30, 0};
-  g.c = RowMap{128, rows_per_batch, 0};
-  g.ldw = ldw;
-  g.conv_shift = -1;
-  g.rowwise_ok = 1;
+  GemmArgs g = gemm_args(X, Wqk, bias, Q, (int)tokens, 2 * dmodel, Kdim, RowMap{ldx, 1L << 30, 0}, RowMap{128, rows_per_batch, 0}, ldw);
   g.span32 = (tokens * ldx) * 2 < (1L << 32) && ((long)g.N * ldw) * 2 < (1L << 32);
   g.qn_wq = wq; g.qn_wk = wk; g.qn_cos = cos; g.qn_sin = sin; g.qn_cs2 = cos_sin_pairs; g.qn_Q = Q; g.qn_K = K;
   g.qn_H = H; g.qn_S = S; g.qn_s0 = s0; g.qn_dmodel = dmodel; g.qn_qscale = q_scale;
-  if (!persistent_ok(g)) return 1;
   return cos_sin_pairs ? launch<EPI_QKNORM_P>(g, (hipStream_t)stream) : launch<EPI_QKNORM>(g, (hipStream_t)stream);
 }
 
@@ -1558,6 +1341,64 @@ extern "C" int mgx_gemm_bf16(const uint16_t* A, const uint16_t* W, const uint16_
                              long c_rpb, long c_bstride, long gate_ld, int epilogue, float beta, void* stream) {
   return mgx_gemm_bf16_sk(A, W, bias, C, gate, aux, ldaux, M, N, K, lda, a_rpb, a_bstride, ldw, ldc, c_rpb, c_bstride, gate_ld,
                           epilogue, beta, nullptr, 0, stream);
+}
+
+// What mgx_gemm_bf16_sk launches for dense operands (lda = ldw = K) of this shape, with (stream_k != 0) or without a workspace,
+// from the functions launch() and the kernels call (gemm_plan.h).  No GPU needed.
+// out[0..5] = kernel family (0: 128x128, 1: persistent 256x256), grid, band, sk_minparts, fix-up blocks (0: nothing is split),
+// XCDs that split their tail (bit x: XCD x).  Returns 6.
+extern "C" int mgx_gemm_plan(int M, int N, int K, int stream_k, int* out, int cap) {
+  MGX_REQUIRE(M > 0 && N > 0 && K > 0 && K % BK == 0 && N % 4 == 0 && out && cap >= 6, "bad shape or output capacity");
+  const bool span32 = (long)M * K * 2 < (1L << 32) && (long)N * K * 2 < (1L << 32);
+  if (!persistent_ok(M, N, K, span32)) {
+    out[0] = 0; out[1] = cdiv(M, BM) * cdiv(N, BN); out[2] = gemm_plan::SMALL_BAND; out[3] = out[4] = out[5] = 0;
+    return 6;
+  }
+  const gemm_plan::PpLaunch p = pp_launch(M, N, K, stream_k != 0);
+  out[0] = 1; out[1] = p.grid; out[2] = pp_band(0, M, N); out[3] = p.sk_minparts; out[4] = p.sk_rmax * 64; out[5] = p.sk_xcds;
+  return 6;
+}
+
+// The work of one block of that launch.  fixup == 0: workgroup `index` of the main kernel; returns its number of units, unit i =
+// out[5 i .. 5 i + 4] = (m0, n0, first K-tile, end K-tile, partial: 1 = its sums go to workspace slot `index`).
+// fixup != 0: fix-up block `index`; returns the number of workspace slots it adds (0: the block is idle), out[0..1] = (m0, n0) of
+// the tile it finishes, out[2 ..] = the slots in the order it adds them.
+extern "C" int mgx_gemm_plan_units(int M, int N, int K, int stream_k, int fixup, int index, int* out, int cap) {
+  int pl[6];
+  if (mgx_gemm_plan(M, N, K, stream_k, pl, 6) != 6) return MGX_ERR_ARG;
+  const int family = pl[0], grid = pl[1], band = pl[2], minparts = pl[3], nfix = pl[4], nkt = K / BK;
+  MGX_REQUIRE(out && index >= 0 && index < (fixup ? nfix : grid), "no such block");
+  if (family == 0) {
+    MGX_REQUIRE(cap >= 5, "output capacity");
+    const int tiles_m = cdiv(M, BM), tiles_n = cdiv(N, BN);
+    const int bid = gemm_plan::xcd_range(tiles_m * tiles_n, index & 7).beg + (index >> 3);
+    long m0, n0;
+    gemm_plan::tile_origin(bid, band, tiles_m, tiles_n, BM, BN, m0, n0);
+    out[0] = (int)m0; out[1] = (int)n0; out[2] = 0; out[3] = nkt; out[4] = 0;
+    return 1;
+  }
+  const int tiles_m = cdiv(M, 256), tiles_n = cdiv(N, 256), nwg = tiles_m * tiles_n, nw = grid / 8;
+  if (fixup) {
+    const gemm_plan::Fixup f = gemm_plan::fixup(nwg, index, nw, minparts, nkt);
+    MGX_REQUIRE(cap >= 2 + f.parts, "output capacity");
+    long m0, n0;
+    gemm_plan::tile_origin(f.tile, band, tiles_m, tiles_n, 256, 256, m0, n0);
+    out[0] = (int)m0; out[1] = (int)n0;
+    for (int p = 0; p < f.parts; ++p) out[2 + p] = f.slot0 + p * f.stride;
+    return f.parts;
+  }
+  const bool sk = nfix > 0;
+  const gemm_plan::XcdRange x = gemm_plan::xcd_range(nwg, index & 7);
+  const gemm_plan::Walk wk = gemm_plan::walk(sk, minparts, x.cnt, nw, index >> 3, nkt);
+  const int n = wk.nfull + wk.ntail;
+  MGX_REQUIRE(cap >= 5 * n, "output capacity");
+  for (int i = 0; i < n; ++i) {
+    const gemm_plan::Unit u = gemm_plan::unit(sk, wk, i, index >> 3, nw, nkt);
+    long m0, n0;
+    gemm_plan::tile_origin(x.beg + u.tile, band, tiles_m, tiles_n, 256, 256, m0, n0);
+    out[5 * i] = (int)m0; out[5 * i + 1] = (int)n0; out[5 * i + 2] = u.k0; out[5 * i + 3] = u.k1; out[5 * i + 4] = u.partial;
+  }
+  return n;
 }
 
 // 3x3 convolution, stride 1, zero padding 1, as an implicit GEMM on the same kernels: x is a zero-bordered NHWC image
@@ -1574,19 +1415,12 @@ extern "C" int mgx_conv3x3_nhwc(const uint16_t* x, const uint16_t* Wt, const uin
   MGX_REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)Wt % 16 == 0) && ((uintptr_t)out % 8 == 0), "operands must be 16-byte aligned");
   const long Wp = Wd + 2;
   MGX_REQUIRE((long)(H + 2) * Wp * C * 2 < (1L << 32) && (long)Cout * 9 * C * 2 < (1L << 32), "image too large for one call");
-  GemmArgs g{};
-  g.A = x; g.W = Wt; g.bias = bias; g.C = out; g.gate = residual ? ones : nullptr; g.aux = nullptr; g.ldaux = 0; g.gate_ld = 0;
-  g.M = H * Wd; g.N = Cout; g.K = 9 * C;
-  g.a = RowMap{C, Wd, Wp * C};                      // output pixel (y, x) -> padded pixel (y, x): tap (0, 0)
-  g.c = RowMap{ld_out, 1L << 30, 0};
-  g.ldw = 9L * C;
-  g.beta = 0.f;
+  // output pixel (y, x) -> padded pixel (y, x): tap (0, 0)
+  GemmArgs g = gemm_args(x, Wt, bias, out, H * Wd, Cout, 9 * C, RowMap{C, Wd, Wp * C}, RowMap{ld_out, 1L << 30, 0}, 9L * C,
+                         residual ? ones : nullptr, 0);
   g.conv_shift = C == 64 ? 0 : (C == 128 ? 1 : (C == 256 ? 2 : 3));
   g.conv_dy = Wp * C; g.conv_dx = C;
-  g.sk_ws = nullptr; g.sk_minparts = 0; g.m_split = 0;
-  g.rowwise_ok = (Cout % 8 == 0) && (ld_out % 8 == 0) && ((uintptr_t)out % 16 == 0) && (!bias || (uintptr_t)bias % 16 == 0) &&
-                 (!residual || (uintptr_t)ones % 16 == 0);
-  g.span32 = 1;
+  g.span32 = 1;                           // (the image-size check above; a row's K range is nine taps, not contiguous)
   hipStream_t st = (hipStream_t)stream;
   return residual ? launch<EPI_BIAS_GATE_RES, true>(g, st) : launch<EPI_BIAS, true>(g, st);
 }

@@ -489,7 +489,7 @@ class FluxTransformer2DModel(torch.nn.Module):
         dev = self.store.device
         mods = {}
         # text stream first: its rows come first in the stacked scratch buffers (nrm / qkv / hid / kept activations) and in
-        # the joint [B, S, d] residual buffer, and its weights first in the parameter store -- problem 1 of the pair launches
+        # the joint [B, S, d] residual buffer, and its weights first in the parameter store
         streams = (("txt", "norm1_context", ("add_q_proj", "add_k_proj", "add_v_proj"), "norm_added_q", "norm_added_k",
                     "to_add_out", "ff_context", w.L, 0),
                    ("img", "norm1", ("to_q", "to_k", "to_v"), "norm_q", "norm_k", "to_out.0", "ff", w.N, w.L))
@@ -515,10 +515,9 @@ class FluxTransformer2DModel(torch.nn.Module):
                 self._qkv_nograd(nrm1[sl[name]], f"{p}.attn.{qkvn[0]}", qkv_buf[sl[name]], w, rows, s0,
                                  self.W32(f"{p}.attn.{nq}.weight"), self.W32(f"{p}.attn.{nk}.weight"), cos, sin)
         elif not (replay and qkv_kept):
-            # both streams' fused QKV projections in one launch (text rows ride the image stream's rounds)
-            ops.gemm_pair(*(x for name, _, qkvn, *_ in streams for x in (
-                Rows.of(nrm1[sl[name]]), fused(self.store.w16, f"{p}.attn.{qkvn[0]}.weight", 3 * d),
-                fused(self.store.w16, f"{p}.attn.{qkvn[0]}.bias", 3 * d), Rows.of(qkv_buf[sl[name]]))), 3 * d, d)
+            for name, _, qkvn, *_ in streams:            # the fused QKV projections
+                ops.gemm(Rows.of(nrm1[sl[name]]), fused(self.store.w16, f"{p}.attn.{qkvn[0]}.weight", 3 * d),
+                         fused(self.store.w16, f"{p}.attn.{qkvn[0]}.bias", 3 * d), Rows.of(qkv_buf[sl[name]]), 3 * d, d)
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in (() if nograd else streams):
             ops.qk_norm_rope(qkv_buf[sl[name]], self.W32(f"{p}.attn.{nq}.weight"), self.W32(f"{p}.attn.{nk}.weight"), cos, sin,
                              w.Q, w.K, w.Vt, B, H, w.S, w.Sp, rows, s0, q_scale=self.q_scale(),
@@ -541,10 +540,10 @@ class FluxTransformer2DModel(torch.nn.Module):
         part = lambda t, name: None if t is None else t[sl[name]]
         if not replay:
             # attention output projections, both streams: x += gate_msa * (O @ W^T + b)
-            ops.gemm_pair(*(x for name, _, _, _, _, outn, *_ in streams for x in (
-                self._stream_rows(O_buf, w, name, d), W16(f"{p}.attn.{outn}.weight"), W16(f"{p}.attn.{outn}.bias"),
-                self._stream_rows(w.X, w, name, d))), d, d, EPI_BIAS_GATE_RES, gate1=mods["txt"][:, 2 * d:3 * d],
-                gate2=mods["img"][:, 2 * d:3 * d], gate_ld=6 * d, aux1=part(aux1, "txt"), aux2=part(aux1, "img"))
+            for name, _, _, _, _, outn, *_ in streams:
+                ops.gemm(self._stream_rows(O_buf, w, name, d), W16(f"{p}.attn.{outn}.weight"), W16(f"{p}.attn.{outn}.bias"),
+                         self._stream_rows(w.X, w, name, d), d, d, EPI_BIAS_GATE_RES, gate=mods[name][:, 2 * d:3 * d],
+                         gate_ld=6 * d, aux=part(aux1, name))
             xm = keep["x_mid"] if keep is not None else (save["x_mid"] if save is not None else None)
             if xm is not None:
                 xm.copy_(w.X)
@@ -557,14 +556,14 @@ class FluxTransformer2DModel(torch.nn.Module):
             pass        # pre-activation kept: no GEMM, and no activation either -- its only reader in the backward, the weight
                         # gradient of ff.net.2, applies GELU inside its operand transpose (flux_backward._wgrad)
         else:
-            ops.gemm_pair(*(x for name, _, _, _, _, _, ffn, *_ in streams for x in (
-                Rows.of(nrm2[sl[name]]), W16(f"{p}.{ffn}.net.0.proj.weight"), W16(f"{p}.{ffn}.net.0.proj.bias"),
-                Rows.of(w.hid[sl[name]]))), 4 * d, d, EPI_BIAS_GELU, aux1=part(hpre, "txt"), aux2=part(hpre, "img"))
+            for name, _, _, _, _, _, ffn, *_ in streams:
+                ops.gemm(Rows.of(nrm2[sl[name]]), W16(f"{p}.{ffn}.net.0.proj.weight"), W16(f"{p}.{ffn}.net.0.proj.bias"),
+                         Rows.of(w.hid[sl[name]]), 4 * d, d, EPI_BIAS_GELU, aux=part(hpre, name))
         if not replay:                                           # y_ff saved: no ff.net.2 GEMM in the recompute
-            ops.gemm_pair(*(x for name, _, _, _, _, _, ffn, *_ in streams for x in (
-                Rows.of(w.hid[sl[name]]), W16(f"{p}.{ffn}.net.2.weight"), W16(f"{p}.{ffn}.net.2.bias"),
-                self._stream_rows(w.X, w, name, d))), d, 4 * d, EPI_BIAS_GATE_RES, gate1=mods["txt"][:, 5 * d:6 * d],
-                gate2=mods["img"][:, 5 * d:6 * d], gate_ld=6 * d, aux1=part(aux2, "txt"), aux2=part(aux2, "img"))
+            for name, _, _, _, _, _, ffn, *_ in streams:
+                ops.gemm(Rows.of(w.hid[sl[name]]), W16(f"{p}.{ffn}.net.2.weight"), W16(f"{p}.{ffn}.net.2.bias"),
+                         self._stream_rows(w.X, w, name, d), d, 4 * d, EPI_BIAS_GATE_RES, gate=mods[name][:, 5 * d:6 * d],
+                         gate_ld=6 * d, aux=part(aux2, name))
         return mods
 
     def _single_block(self, i, w, st, cos, sin, save=None, mod_in=None, keep=None, replay=False, x_in=None):

@@ -276,20 +276,6 @@ def _dgrad(model, tr, dC: Rows, N, K, wname, out: Rows, rows=None, epi=EPI_BIAS,
     ops.gemm(dC, Wt[row_lo:row_hi], None, out, row_hi - row_lo, N, epi, aux=aux, ldaux=ldaux, gate=gate, gate_ld=0)
 
 
-def _dgrad_pair(model, tr, dC1: Rows, wname1, out1: Rows, dC2: Rows, wname2, out2: Rows, N, K, rows=None, epi=EPI_BIAS, aux1=None,
-                aux2=None, ldaux=None):
-    """`_dgrad` for the text- and the image-stream Linear of a double block in ONE launch (`ops.gemm_pair`): both transposed
-    weights side by side in the Wt scratch, problem 1 = the text stream."""
-    st = model.store
-    Wts = []
-    for j, wname in enumerate((wname1, wname2)):
-        W = st.fused(st.w16, wname, N) if rows else st.view(st.w16, wname)
-        Wt = tr.Wt[j * K * N:(j + 1) * K * N].view(K, N)
-        ops.transpose(Rows.of(W), K, Wt, N)
-        Wts.append(Wt)
-    ops.gemm_pair(dC1, Wts[0], None, out1, dC2, Wts[1], None, out2, K, N, epi, aux1=aux1, aux2=aux2, ldaux=ldaux)
-
-
 def _attn_bwd(w, Q, K, V, Qt, Kt, O, dO, lse, tr, B, H, S, Sp, ldo, o_bstride, scale):
     """The attention backward of one block into tr.dQ / dK / dV.  On a padded workspace (w.kv_len set; every buffer allocated
     at S % 256 == 0) the masked-tail pair: rows >= kv_len contribute nothing and their dQ / dK / dV rows come back zero."""
@@ -402,8 +388,7 @@ def _backward(model, w, tr, sv, dout):
         grad_ready(p)
 
     # ---------------- double blocks (reverse)
-    # text stream first = problem 1 of the pair launches (its rows come first in every stacked buffer); the two streams'
-    # input-gradient GEMMs go out as one launch each, everything else per stream
+    # text stream first (its rows come first in every stacked buffer)
     streams = (("txt", "norm1_context", ("add_q_proj", "add_k_proj", "add_v_proj"), "norm_added_q", "norm_added_k",
                 "to_add_out", "ff_context", L, 0),
                ("img", "norm1", ("to_q", "to_k", "to_v"), "norm_q", "norm_k", "to_out.0", "ff", N, L))
@@ -433,14 +418,14 @@ def _backward(model, w, tr, sv, dout):
             a_op = [(Rows.of(kept["hid_pre"][sl[name]]), 4 * d, True)] if kept is not None and "hid_pre" in kept \
                 else Rows.of(w.hid[sl[name]])
             _wgrad(model, tr, a_op, 4 * d, Rows.of(tr.dy[sl[name]]), d, f"{p}.{ffn}.net.2.weight", f"{p}.{ffn}.net.2.bias")
-        _dgrad_pair(model, tr, Rows.of(tr.dy[sl["txt"]]), f"{p}.ff_context.net.2.weight", Rows.of(dh_all[sl["txt"]]),
-                    Rows.of(tr.dy[sl["img"]]), f"{p}.ff.net.2.weight", Rows.of(dh_all[sl["img"]]), d, 4 * d, epi=EPI_DGELU,
-                    aux1=save["hid_pre"][sl["txt"]], aux2=save["hid_pre"][sl["img"]], ldaux=4 * d)
+        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
+            _dgrad(model, tr, Rows.of(tr.dy[sl[name]]), d, 4 * d, f"{p}.{ffn}.net.2.weight", Rows.of(dh_all[sl[name]]),
+                   epi=EPI_DGELU, aux=save["hid_pre"][sl[name]], ldaux=4 * d)
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             _wgrad(model, tr, Rows.of(save["nrm2"][sl[name]]), d, Rows.of(dh_all[sl[name]]), 4 * d, f"{p}.{ffn}.net.0.proj.weight",
                    f"{p}.{ffn}.net.0.proj.bias")
-        _dgrad_pair(model, tr, Rows.of(dh_all[sl["txt"]]), f"{p}.ff_context.net.0.proj.weight", Rows.of(tr.dnrm[sl["txt"]]),
-                    Rows.of(dh_all[sl["img"]]), f"{p}.ff.net.0.proj.weight", Rows.of(tr.dnrm[sl["img"]]), 4 * d, d)
+        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
+            _dgrad(model, tr, Rows.of(dh_all[sl[name]]), 4 * d, d, f"{p}.{ffn}.net.0.proj.weight", Rows.of(tr.dnrm[sl[name]]))
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             m, dm = mods[name], dmods[name]
             dXs = srows(tr.dX, name, d)
@@ -450,8 +435,8 @@ def _backward(model, w, tr, sv, dout):
             ops.gate_bwd(dXs, save["y_attn"][sl[name]], m[:, 2 * d:3 * d], 6 * d, tr.dy[sl[name]], dm[:, 2 * d:3 * d], B, rows, d)
             _wgrad(model, tr, srows(O_b, name, d), d, Rows.of(tr.dy[sl[name]]), d, f"{p}.attn.{outn}.weight",
                    f"{p}.attn.{outn}.bias")
-        _dgrad_pair(model, tr, Rows.of(tr.dy[sl["txt"]]), f"{p}.attn.to_add_out.weight", srows(dO3, "txt", d),
-                    Rows.of(tr.dy[sl["img"]]), f"{p}.attn.to_out.0.weight", srows(dO3, "img", d), d, d)
+        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
+            _dgrad(model, tr, Rows.of(tr.dy[sl[name]]), d, d, f"{p}.attn.{outn}.weight", srows(dO3, name, d))
         _attn_bwd(w, w.Q, w.K, save["V"], save["Qt"], save["Kt"], O_b, dO3, lse_b, tr, B, H, S, Sp, d, S * d, scale)
         qkv_b = kept["qkv"] if kept is not None and "qkv" in kept else w.qkv
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
@@ -460,8 +445,9 @@ def _backward(model, w, tr, sv, dout):
                                  store.view(g32, f"{p}.attn.{nk}.weight"), B, H, S, Sp, rows, s0, q_scale=q_scale)
             _wgrad(model, tr, Rows.of(save["nrm1"][sl[name]]), d, Rows.of(dqkv_all[sl[name]]), 3 * d, f"{p}.attn.{qkvn[0]}.weight",
                    f"{p}.attn.{qkvn[0]}.bias", rows=True)
-        _dgrad_pair(model, tr, Rows.of(dqkv_all[sl["txt"]]), f"{p}.attn.add_q_proj.weight", Rows.of(tr.dnrm[sl["txt"]]),
-                    Rows.of(dqkv_all[sl["img"]]), f"{p}.attn.to_q.weight", Rows.of(tr.dnrm[sl["img"]]), 3 * d, d, rows=True)
+        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
+            _dgrad(model, tr, Rows.of(dqkv_all[sl[name]]), 3 * d, d, f"{p}.attn.{qkvn[0]}.weight", Rows.of(tr.dnrm[sl[name]]),
+                   rows=True)
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             m, dm = mods[name], dmods[name]
             ops.ln_modulate_bwd(tr.dnrm[sl[name]], srows(tr.block_in[i], name, d), m[:, d:2 * d], 6 * d, srows(tr.dX, name, d),

@@ -220,35 +220,11 @@ def test_gelu_rows_is_the_gemm_epilogue_on_every_bf16_value(N):
     assert torch.allclose(C[:, 0].float()[big], torch.nn.functional.gelu(x[big], approximate="tanh"), rtol=2.0 ** -7, atol=1e-6)
 
 
-# ---- stream-K tail (csrc/gemm.hip, sk_tail / gemm_sk_fixup_kernel): shapes whose last round is split along K under the
-# default cost rule.  (tiles, per-XCD tail R, parts P = min(8, 32 // R)): 128 tiles = no whole round, R = 16, every tile in 2
+# ---- stream-K tail (csrc/gemm_plan.h walk / fixup, gemm_sk_fixup_kernel): shapes whose last round is split along K under the
+# default cost rule -- tests/test_gemm_plan.py asks the library that they are, without a GPU.  (tiles, per-XCD tail R, parts P = min(8, 32 // R)): 128 tiles = no whole round, R = 16, every tile in 2
 # parts; 296 tiles = one whole round + R = 5, 6 parts (30 of an XCD's 32 workgroups busy); 356 tiles with a ragged M edge =
 # one round + R = 13 on four XCDs and 12 on the others, 2 parts; 576 tiles = 2 rounds + R = 8, 4 parts.
 SK_SHAPES = [(2048, 4096, 8192), (2048, 9472, 4096), (1024 - 17, 22784, 8192), (3072, 12288, 4096)]
-
-
-def _sk_splits(M, N, K):
-    """The cost rule of csrc/gemm.hip `launch()` restated, per XCD: T = 0.0247 K us; P = min(8, 32 // R);
-    split <=> P >= max(2, floor(1.25 / (1 - 40 / T)) + 1) and K / 64 >= 4 P."""
-    import math
-    tiles = math.ceil(M / 256) * math.ceil(N / 256)
-    room = 1 - 40.0 / (K * 0.0247)
-    minparts = 9 if room <= 0 else max(2, math.floor(1.25 / room) + 1)
-    q, rem = tiles // 8, tiles % 8
-    out = []
-    for cnt in [q + (x < rem) for x in range(8)]:
-        R = cnt % 32
-        P = min(8, 32 // R) if R else 0
-        out.append(P >= 2 and P >= minparts and K // 64 >= 4 * P)
-    return out
-
-
-def test_stream_k_rule_splits_the_test_shapes():
-    """The shapes of this file's stream-K tests ARE split -- otherwise they would silently test the unsplit kernel."""
-    for shp in SK_SHAPES + [(2048, 4096, 8192 + 64), (3072, 12288, 4096 + 64), (6144, 3072, 4096)]:
-        assert all(_sk_splits(*shp)), shp
-    assert not any(_sk_splits(4608, 3072, 15360))       # R = 27: cannot be cut in two, left whole
-    assert not any(_sk_splits(3072, 3072, 28672))       # R = 18 likewise
 
 
 @pytest.mark.parametrize("M,N,K", SK_SHAPES)
@@ -332,87 +308,6 @@ def test_gemm_stream_k_f32_accumulate(M, N, K, beta):
     assert torch.equal(outs[0], outs[1])
     err = ((outs[0].double() - ref).norm() / ref.norm()).item()
     assert err < 1e-5, err
-
-
-# ---- pair launches (mgx_gemm_bf16_pair): the text- and image-stream Linear of a double block as one walk of the persistent kernel
-@pytest.mark.parametrize("epi", [EPI_BIAS, EPI_GELU, EPI_GATE_RES, EPI_DGELU])
-@pytest.mark.parametrize("B,L,Nimg,N,K,swap_w", [(4, 512, 1024, 3072, 1024, False), (2, 512, 4096, 1536, 512, True), (3, 256, 2048 + 64, 2048, 256, False),
-                                                (4, 512, 1024, 3072, 4096, True)])    # the last: 288 tiles, K = 4096 -> pair AND stream-K tail
-def test_gemm_pair_equals_two_launches(epi, B, L, Nimg, N, K, swap_w):
-    """Joint [B, S, .] buffers with the text rows first (row-batched operands, as flux.py hands them over) or stacked plain
-    matrices; weights in either address order.  With the stream-K tail off every tile is computed whole by the same K-loop in
-    both forms: the pair launch must equal the two single launches BIT FOR BIT; with it on, to summation-order accuracy."""
-    from mixgrpo_amd import ops
-    from mixgrpo_amd.ops import Rows
-    g = torch.Generator().manual_seed(B * 1000 + N + K + epi)
-    S = L + Nimg
-    joint_a = epi in (EPI_GATE_RES,)                         # A from a joint [B, S, K] buffer (to_out: the attention output)
-    Wboth = (torch.randn(2, N, K, generator=g) * 0.05).bfloat16().cuda()
-    Wt, Wi = (Wboth[1], Wboth[0]) if swap_w else (Wboth[0], Wboth[1])
-    bias = (torch.randn(2, N, generator=g) * 0.2).bfloat16().cuda()
-    if joint_a:
-        Abuf = (torch.randn(B, S, K, generator=g) * 0.5).bfloat16().cuda()
-        A1, A2 = Rows(Abuf, B * L, K, L, S * K), Rows(Abuf[0, L:], B * Nimg, K, Nimg, S * K)
-    else:
-        Abuf = (torch.randn(B * S, K, generator=g) * 0.5).bfloat16().cuda()
-        A1, A2 = Rows.of(Abuf[:B * L]), Rows.of(Abuf[B * L:])
-    C0 = torch.randn(B, S, N, generator=g).bfloat16().cuda()
-    gate = torch.randn(2, B, N, generator=g).bfloat16().cuda() if epi == EPI_GATE_RES else None
-    aux0 = torch.randn(B * S, N, generator=g).bfloat16().cuda() if epi == EPI_DGELU else \
-        (torch.full((B * S, N), 7.0, dtype=torch.bfloat16, device="cuda") if epi in (EPI_GELU, EPI_GATE_RES) else None)
-
-    pair_default = ops.GEMM_PAIR
-
-    def run(pair, sk):
-        C = C0.clone()
-        aux = None if aux0 is None else aux0.clone()
-        if epi == EPI_GATE_RES:                              # C joint [B, S, N], text rows first
-            C1, C2 = Rows(C, B * L, N, L, S * N), Rows(C[0, L:], B * Nimg, N, Nimg, S * N)
-        else:                                                # C stacked
-            Cs = C.view(B * S, N)
-            C1, C2 = Rows.of(Cs[:B * L]), Rows.of(Cs[B * L:])
-        a1 = None if aux is None else aux[:B * L]
-        a2 = None if aux is None else aux[B * L:]
-        g1 = None if gate is None else gate[0]
-        g2 = None if gate is None else gate[1]
-        ops.GEMM_STREAM_K, ops.GEMM_PAIR = sk, pair
-        try:
-            ops.gemm_pair(A1, Wt, bias[0], C1, A2, Wi, bias[1], C2, N, K, epi, gate1=g1, gate2=g2, gate_ld=N, aux1=a1, aux2=a2)
-        finally:
-            ops.GEMM_STREAM_K, ops.GEMM_PAIR = True, pair_default
-        torch.cuda.synchronize()
-        return C, aux
-
-    Cp, ap = run(True, False)
-    Cs_, as_ = run(False, False)
-    assert torch.equal(Cp, Cs_)
-    if aux0 is not None and epi != EPI_DGELU:
-        assert torch.equal(ap, as_)
-    Ck, _ = run(True, True)
-    assert (Ck != Cs_).float().mean().item() < 2e-3
-    # and against the fp32 reference, per stream
-    Ad = Abuf.view(B, S, K) if joint_a else None
-    for which, (W_, sl_) in enumerate(((Wt, slice(0, L)), (Wi, slice(L, S)))):
-        if joint_a:
-            a = Ad[:, sl_].reshape(-1, K)
-        else:
-            a = (Abuf[:B * L] if which == 0 else Abuf[B * L:])
-        y = (a.float() @ W_.float().t() + bias[which].float()).bfloat16().float()
-        if epi == EPI_GATE_RES:
-            rows = sl_.stop - sl_.start
-            gsel = gate[which].float().repeat_interleave(rows, dim=0)
-            ref = C0[:, sl_].reshape(-1, N).float() + (gsel * y).bfloat16().float()
-            out, amp = Cp[:, sl_].reshape(-1, N), gsel.abs() + 0.01
-        else:
-            out = Cp.view(B * S, N)[:B * L] if which == 0 else Cp.view(B * S, N)[B * L:]
-            if epi == EPI_BIAS:
-                ref, amp = y, 0.0
-            elif epi == EPI_GELU:
-                ref, amp = _gelu(y), 1.2
-            else:
-                au = aux0[:B * L] if which == 0 else aux0[B * L:]
-                ref, amp = y * _dgelu(au.float().cpu()).cuda(), 1.2
-        _close_bf16(out, ref.bfloat16(), y, amp)
 
 
 @pytest.mark.parametrize("M,N", [(4608, 12288), (1000, 256), (64 * 3 + 8, 136)])
