@@ -199,7 +199,7 @@ class _Work:
     slices of it (`view`), so the rollout (B = G), the shared first step (B = 1) and the replay micro-batches share one
     allocation instead of one per batch size."""
 
-    kv_len = None     # set by a padded forward / backward (ops.ATTN_PAD_KV) for the length of one call: rows >= kv_len of S are padding
+    kv_len = None     # a padded call (ops.ATTN_PAD_KV) works on a `_WorkView` that carries its kv_len: rows >= kv_len of S are padding
 
     def __init__(self, cfg, B, L, N, device):
         d, H, hd = cfg.dim, cfg.num_attention_heads, cfg.attention_head_dim
@@ -232,18 +232,18 @@ class _Work:
                         torch.empty(3 * self.B * H, dtype=F32, device=self.X.device))
         return self._f8
 
-    def view(self, B):
-        return self if B == self.B else _WorkView(self, B)
+    def view(self, B, kv_len=None):
+        return self if B == self.B and kv_len is None else _WorkView(self, B, kv_len)
 
 
 class _WorkView:
-    """The first B batches of a `_Work` (all buffers are batch-major and contiguous, so these are plain prefixes)."""
+    """The first B batches of a `_Work` (all buffers are batch-major and contiguous, so these are plain prefixes), for one
+    call: `kv_len` is that call's valid sequence length when it runs padded, and stays with the view (a training forward's
+    view serves its backward)."""
 
-    kv_len = None
-
-    def __init__(self, base, B):
+    def __init__(self, base, B, kv_len=None):
         assert B <= base.B
-        self.base, self.B, self.L, self.N, self.S, self.Sp = base, B, base.L, base.N, base.S, base.Sp
+        self.base, self.B, self.L, self.N, self.S, self.Sp, self.kv_len = base, B, base.L, base.N, base.S, base.Sp, kv_len
         M = B * base.S
         self.X, self.Q, self.K, self.Vt, self.O, self.cat = (t[:B] for t in (base.X, base.Q, base.K, base.Vt, base.O, base.cat))
         self.nrm, self.qkv, self.hid = base.nrm[:M], base.qkv[:M], base.hid[:M]
@@ -346,8 +346,9 @@ class FluxTransformer2DModel(torch.nn.Module):
         return sum(b.train.qkv_kept() for b in self._work.values() if b.train is not None and b.train.keep is not None)
 
     # ------------------------------------------------------------------ forward
-    def _workspace(self, B, L, N):
-        """Workspace view for batch B of the (L, N) shape; the base grows to the largest batch seen."""
+    def _workspace(self, B, L, N, kv_len=None):
+        """Workspace view for batch B of the (L, N) shape; the base grows to the largest batch seen.  `kv_len`: the call runs
+        padded (ops.ATTN_PAD_KV) and its view says so to `_attn` / `_attn_bwd`; the base never does."""
         key = (L, N)
         base = self._work.get(key)
         if base is None or base.B < B:
@@ -359,7 +360,7 @@ class FluxTransformer2DModel(torch.nn.Module):
             torch.cuda.empty_cache()     # hand the outgrown buffers back before allocating the larger ones
             base = _Work(self.cfg, B, L, N, self.store.device)
             self._work[key] = base
-        return base.view(B)
+        return base.view(B, kv_len)
 
     def _attn(self, w, O, lse, ldo, o_bstride):
         """Joint attention of the current Q / K / Vt workspace into O (+ LSE).  `attention_dtype == "fp8"` (BASELINE.json
@@ -478,27 +479,28 @@ class FluxTransformer2DModel(torch.nn.Module):
             return Rows(t, w.B * w.L, width, w.L, w.S * width)
         return Rows(t[0, w.L:], w.B * w.N, width, w.N, w.S * width)
 
-    def _double_block(self, i, w, st, cos, sin, save=None, mods_in=None, keep=None, replay=False, x_in=None):
-        """`save`: keep the block's intermediates for the backward walk (recompute pass).  `keep`: per-block buffers
-        {O, lse, y_attn, y_ff, x_mid} written by the training forward; with `replay` the recompute pass reads them
-        back instead of re-running attention and the two output projections (to_out / ff.net.2), and reads the block's
-        input from `x_in` (the saved block input: the residual stream is not written in this mode, so no copy of it)."""
+    def _streams(self, w):
+        """The two streams of a double block as (name, norm, q | k | v projections, norm_q, norm_k, out projection, ff, rows per
+        batch, first sequence row), and each stream's rows of the stacked scratch buffers (nrm / qkv / hid / kept activations).
+        Text first: its rows come first in those buffers and in the joint [B, S, d] residual buffer, and its weights first in
+        the parameter store."""
+        streams = (("txt", "norm1_context", ("add_q_proj", "add_k_proj", "add_v_proj"), "norm_added_q", "norm_added_k",
+                    "to_add_out", "ff_context", w.L, 0),
+                   ("img", "norm1", ("to_q", "to_k", "to_v"), "norm_q", "norm_k", "to_out.0", "ff", w.N, w.L))
+        return streams, {"txt": slice(0, w.B * w.L), "img": slice(w.B * w.L, w.B * w.S)}
+
+    def _double_block(self, i, w, st, cos, sin, pl, mods_in=None):
+        """One pass through double block `i` as its plan `pl` lays it out (flux_backward._BlockPlan: the buffer of every role
+        and which steps run).  `mods_in`: the forward's modulations, for a recompute pass."""
         cfg, d, H = self.cfg, self.cfg.dim, self.cfg.num_attention_heads
         p = f"transformer_blocks.{i}"
         B = w.B
         dev = self.store.device
         mods = {}
-        # text stream first: its rows come first in the stacked scratch buffers (nrm / qkv / hid / kept activations) and in
-        # the joint [B, S, d] residual buffer, and its weights first in the parameter store
-        streams = (("txt", "norm1_context", ("add_q_proj", "add_k_proj", "add_v_proj"), "norm_added_q", "norm_added_k",
-                    "to_add_out", "ff_context", w.L, 0),
-                   ("img", "norm1", ("to_q", "to_k", "to_v"), "norm_q", "norm_k", "to_out.0", "ff", w.N, w.L))
-        row0 = {"txt": 0, "img": w.B * w.L}     # row offsets inside the per-stream scratch buffers
-        sl = {n: slice(row0[n], row0[n] + B * r) for n, r in (("txt", w.L), ("img", w.N))}
+        streams, sl = self._streams(w)
         W16, fused = self.W, self.store.fused
-        qkv_kept = keep is not None and "qkv" in keep           # QKV output kept by the forward: no GEMM in the recompute
-        qkv_buf = keep["qkv"] if qkv_kept else w.qkv
-        nrm1 = w.nrm if save is None else save["nrm1"]
+        if pl.restore is not None:
+            w.X.copy_(pl.restore)                               # full recompute rewrites the residual stream
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             if mods_in is not None:
                 m = mods_in[name]
@@ -506,112 +508,83 @@ class FluxTransformer2DModel(torch.nn.Module):
                 m = torch.empty(B, 6 * d, dtype=BF16, device=dev)
                 ops.skinny_linear(st, W16(f"{p}.{norm}.linear.weight"), W16(f"{p}.{norm}.linear.bias"), m, 6 * d, d)
             mods[name] = m
-            Xs = self._stream_rows(w.X if x_in is None else x_in, w, name, d)
-            ops.ln_modulate(Xs, m[:, 0:d], m[:, d:2 * d], 6 * d, nrm1[sl[name]], d)
-        nograd = save is None and keep is None
-        if nograd:
+            ops.ln_modulate(self._stream_rows(pl.x_in, w, name, d), m[:, 0:d], m[:, d:2 * d], 6 * d, pl.nrm1[sl[name]], d)
+        if pl.fused_qkv:
             # no-grad forward (the rollout): V^T straight from the value projection, QK-norm / RoPE in the q | k projection's epilogue
             for name, _, qkvn, nq, nk, _, _, rows, s0 in streams:
-                self._qkv_nograd(nrm1[sl[name]], f"{p}.attn.{qkvn[0]}", qkv_buf[sl[name]], w, rows, s0,
+                self._qkv_nograd(pl.nrm1[sl[name]], f"{p}.attn.{qkvn[0]}", pl.qkv[sl[name]], w, rows, s0,
                                  self.W32(f"{p}.attn.{nq}.weight"), self.W32(f"{p}.attn.{nk}.weight"), cos, sin)
-        elif not (replay and qkv_kept):
-            for name, _, qkvn, *_ in streams:            # the fused QKV projections
-                ops.gemm(Rows.of(nrm1[sl[name]]), fused(self.store.w16, f"{p}.attn.{qkvn[0]}.weight", 3 * d),
-                         fused(self.store.w16, f"{p}.attn.{qkvn[0]}.bias", 3 * d), Rows.of(qkv_buf[sl[name]]), 3 * d, d)
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in (() if nograd else streams):
-            ops.qk_norm_rope(qkv_buf[sl[name]], self.W32(f"{p}.attn.{nq}.weight"), self.W32(f"{p}.attn.{nk}.weight"), cos, sin,
-                             w.Q, w.K, w.Vt, B, H, w.S, w.Sp, rows, s0, q_scale=self.q_scale(),
-                             **({} if save is None else dict(V=save["V"], Qt=save["Qt"], Kt=save["Kt"])))
-        # the attention output lives in the block's keep buffer when there is one (written here, read by the backward):
-        # no copy between the workspace and the kept tensor
-        O_buf = keep["O"] if keep is not None else w.O
-        if not replay:
-            self._attn(w, O_buf, keep["lse"] if keep is not None else (w.lse if save is not None else None), d, w.S * d)
-        aux1 = aux2 = hpre = None
-        if keep is not None and not replay:
-            aux1, aux2 = keep["y_attn"], keep["y_ff"]
-        elif save is not None:
-            aux1, aux2 = save["y_attn"], save["y_ff"]
-        ff_kept = keep is not None and "hid_pre" in keep
-        if save is not None:
-            hpre = save["hid_pre"]                              # (with ff_kept this IS the kept buffer)
-        elif ff_kept:
-            hpre = keep["hid_pre"]
+        else:
+            for name, _, qkvn, *_ in (streams if pl.run_qkv else ()):        # the fused QKV projections
+                ops.gemm(Rows.of(pl.nrm1[sl[name]]), fused(self.store.w16, f"{p}.attn.{qkvn[0]}.weight", 3 * d),
+                         fused(self.store.w16, f"{p}.attn.{qkvn[0]}.bias", 3 * d), Rows.of(pl.qkv[sl[name]]), 3 * d, d)
+            for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
+                ops.qk_norm_rope(pl.qkv[sl[name]], self.W32(f"{p}.attn.{nq}.weight"), self.W32(f"{p}.attn.{nk}.weight"), cos, sin,
+                                 w.Q, w.K, w.Vt, B, H, w.S, w.Sp, rows, s0, V=pl.V, Qt=pl.Qt, Kt=pl.Kt, q_scale=self.q_scale())
+        if pl.run_attn:
+            self._attn(w, pl.O, pl.lse, d, w.S * d)
         part = lambda t, name: None if t is None else t[sl[name]]
-        if not replay:
+        if pl.run_out:
             # attention output projections, both streams: x += gate_msa * (O @ W^T + b)
             for name, _, _, _, _, outn, *_ in streams:
-                ops.gemm(self._stream_rows(O_buf, w, name, d), W16(f"{p}.attn.{outn}.weight"), W16(f"{p}.attn.{outn}.bias"),
+                ops.gemm(self._stream_rows(pl.O, w, name, d), W16(f"{p}.attn.{outn}.weight"), W16(f"{p}.attn.{outn}.bias"),
                          self._stream_rows(w.X, w, name, d), d, d, EPI_BIAS_GATE_RES, gate=mods[name][:, 2 * d:3 * d],
-                         gate_ld=6 * d, aux=part(aux1, name))
-            xm = keep["x_mid"] if keep is not None else (save["x_mid"] if save is not None else None)
-            if xm is not None:
-                xm.copy_(w.X)
-        x_mid = keep["x_mid"] if replay else w.X                 # replay: saved, no to_out GEMM in the recompute
-        nrm2 = w.nrm if save is None else save["nrm2"]
+                         gate_ld=6 * d, aux=part(pl.y_attn, name))
+            if pl.x_mid is not None:
+                pl.x_mid.copy_(w.X)
+        x_mid = w.X if pl.run_out else pl.x_mid                  # replay: kept, the residual stream is not written
         for name in ("txt", "img"):
             m = mods[name]
-            ops.ln_modulate(self._stream_rows(x_mid, w, name, d), m[:, 3 * d:4 * d], m[:, 4 * d:5 * d], 6 * d, nrm2[sl[name]], d)
-        if replay and ff_kept:
-            pass        # pre-activation kept: no GEMM, and no activation either -- its only reader in the backward, the weight
-                        # gradient of ff.net.2, applies GELU inside its operand transpose (flux_backward._wgrad)
-        else:
-            for name, _, _, _, _, _, ffn, *_ in streams:
-                ops.gemm(Rows.of(nrm2[sl[name]]), W16(f"{p}.{ffn}.net.0.proj.weight"), W16(f"{p}.{ffn}.net.0.proj.bias"),
-                         Rows.of(w.hid[sl[name]]), 4 * d, d, EPI_BIAS_GELU, aux=part(hpre, name))
-        if not replay:                                           # y_ff saved: no ff.net.2 GEMM in the recompute
-            for name, _, _, _, _, _, ffn, *_ in streams:
-                ops.gemm(Rows.of(w.hid[sl[name]]), W16(f"{p}.{ffn}.net.2.weight"), W16(f"{p}.{ffn}.net.2.bias"),
-                         self._stream_rows(w.X, w, name, d), d, 4 * d, EPI_BIAS_GATE_RES, gate=mods[name][:, 5 * d:6 * d],
-                         gate_ld=6 * d, aux=part(aux2, name))
+            ops.ln_modulate(self._stream_rows(x_mid, w, name, d), m[:, 3 * d:4 * d], m[:, 4 * d:5 * d], 6 * d, pl.nrm2[sl[name]], d)
+        # (pre-activation kept: no GEMM in the replay, and no activation either -- its only reader in the backward, the weight
+        # gradient of ff.net.2, applies GELU inside its operand transpose: flux_backward._wgrad)
+        for name, _, _, _, _, _, ffn, *_ in (streams if pl.run_ff else ()):
+            ops.gemm(Rows.of(pl.nrm2[sl[name]]), W16(f"{p}.{ffn}.net.0.proj.weight"), W16(f"{p}.{ffn}.net.0.proj.bias"),
+                     Rows.of(w.hid[sl[name]]), 4 * d, d, EPI_BIAS_GELU, aux=part(pl.hid_pre, name))
+        for name, _, _, _, _, _, ffn, *_ in (streams if pl.run_out else ()):
+            ops.gemm(Rows.of(w.hid[sl[name]]), W16(f"{p}.{ffn}.net.2.weight"), W16(f"{p}.{ffn}.net.2.bias"),
+                     self._stream_rows(w.X, w, name, d), d, 4 * d, EPI_BIAS_GATE_RES, gate=mods[name][:, 5 * d:6 * d],
+                     gate_ld=6 * d, aux=part(pl.y_ff, name))
         return mods
 
-    def _single_block(self, i, w, st, cos, sin, save=None, mod_in=None, keep=None, replay=False, x_in=None):
-        """`keep` / `replay` / `x_in`: as in `_double_block`, with per-block buffers {O, lse, y_attn}."""
+    def _single_block(self, i, w, st, cos, sin, pl, mod_in=None):
+        """As `_double_block`.  [O | mlp] lives in `w.cat` at row stride 5d, except in a lean replay (`pl.lean`), which builds
+        no such operand."""
         cfg, d, H = self.cfg, self.cfg.dim, self.cfg.num_attention_heads
         p = f"single_transformer_blocks.{i}"
         B, S = w.B, w.S
         M = B * S
+        if pl.restore is not None:
+            w.X.copy_(pl.restore)
         if mod_in is not None:
             m = mod_in
         else:
             m = torch.empty(B, 3 * d, dtype=BF16, device=self.store.device)
             ops.skinny_linear(st, self.W(f"{p}.norm.linear.weight"), self.W(f"{p}.norm.linear.bias"), m, 3 * d, d)
-        Xa = Rows(w.X if x_in is None else x_in, M, d, S, S * d)
-        nrm = w.nrm if save is None else save["nrm1"]
-        ops.ln_modulate(Xa, m[:, 0:d], m[:, d:2 * d], 3 * d, nrm, d)
-        qkv_kept = keep is not None and "qkv" in keep           # as in `_double_block`
-        qkv = keep["qkv"] if qkv_kept else w.qkv
-        nograd = save is None and keep is None
-        if nograd:
-            self._qkv_nograd(nrm, f"{p}.attn.to_q", qkv, w, S, 0, self.W32(f"{p}.attn.norm_q.weight"),
-                             self.W32(f"{p}.attn.norm_k.weight"), cos, sin)
-        elif not (replay and qkv_kept):
-            ops.gemm(Rows.of(nrm), self.store.fused(self.store.w16, f"{p}.attn.to_q.weight", 3 * d),
-                     self.store.fused(self.store.w16, f"{p}.attn.to_q.bias", 3 * d), Rows.of(qkv), 3 * d, d)
+        Xa = Rows(pl.x_in, M, d, S, S * d)
+        ops.ln_modulate(Xa, m[:, 0:d], m[:, d:2 * d], 3 * d, pl.nrm1, d)
+        wq, wk = self.W32(f"{p}.attn.norm_q.weight"), self.W32(f"{p}.attn.norm_k.weight")
+        if pl.fused_qkv:
+            self._qkv_nograd(pl.nrm1, f"{p}.attn.to_q", pl.qkv, w, S, 0, wq, wk, cos, sin)
+        elif pl.run_qkv:
+            ops.gemm(Rows.of(pl.nrm1), self.store.fused(self.store.w16, f"{p}.attn.to_q.weight", 3 * d),
+                     self.store.fused(self.store.w16, f"{p}.attn.to_q.bias", 3 * d), Rows.of(pl.qkv), 3 * d, d)
         cat2 = w.cat.view(M, 5 * d)
-        # the pre-activation (when kept) goes to columns 3d..7d of the [M, 7d] gradient staging buffer's twin
-        ff_kept = keep is not None and "hid_pre" in keep
-        if replay and ff_kept:                       # pre-activation kept by the forward (`save["hid_pre"]` IS that buffer):
-            pass                                     # no GEMM and no [O | mlp] operand (flux_backward: `lean`)
-        else:
-            ops.gemm(Rows.of(nrm), self.W(f"{p}.proj_mlp.weight"), self.W(f"{p}.proj_mlp.bias"),
-                     Rows(cat2[0, d:], M, 5 * d), 4 * d, d, EPI_BIAS_GELU,
-                     aux=save["hid_pre"] if save is not None else (keep["hid_pre"] if ff_kept else None))
-        if not nograd:
-            ops.qk_norm_rope(qkv, self.W32(f"{p}.attn.norm_q.weight"), self.W32(f"{p}.attn.norm_k.weight"), cos, sin,
-                             w.Q, w.K, w.Vt, B, H, S, w.Sp, S, 0, q_scale=self.q_scale(),
-                             **({} if save is None else dict(V=save["V"], Qt=save["Qt"], Kt=save["Kt"])))
-        if replay:                                   # attention output and proj_out result were kept by the forward
-            if not ff_kept:
-                w.cat[:, :, :d].copy_(keep["O"])     # (the wgrad of proj_out then reads [O | mlp] as one [M, 5d] operand)
-            return m
-        self._attn(w, w.cat, keep["lse"] if keep is not None else (w.lse if save is not None else None), 5 * d, S * 5 * d)
-        if keep is not None:
-            keep["O"].copy_(w.cat[:, :, :d])
-        aux = keep["y_attn"] if keep is not None else (None if save is None else save["y_attn"])
-        ops.gemm(Rows.of(cat2), self.W(f"{p}.proj_out.weight"), self.W(f"{p}.proj_out.bias"), Xa, d, 5 * d,
-                 EPI_BIAS_GATE_RES, gate=m[:, 2 * d:3 * d], gate_ld=3 * d, aux=aux)
+        if pl.run_ff:
+            ops.gemm(Rows.of(pl.nrm1), self.W(f"{p}.proj_mlp.weight"), self.W(f"{p}.proj_mlp.bias"),
+                     Rows(cat2[0, d:], M, 5 * d), 4 * d, d, EPI_BIAS_GELU, aux=pl.hid_pre)
+        if not pl.fused_qkv:
+            ops.qk_norm_rope(pl.qkv, wq, wk, cos, sin, w.Q, w.K, w.Vt, B, H, S, w.Sp, S, 0, V=pl.V, Qt=pl.Qt, Kt=pl.Kt,
+                             q_scale=self.q_scale())
+        if pl.run_attn:
+            self._attn(w, pl.O, pl.lse, pl.ldo, S * pl.ldo)
+            if pl.O_keep is not None:
+                pl.O_keep.copy_(w.cat[:, :, :d])
+        elif not pl.lean:
+            w.cat[:, :, :d].copy_(pl.O_keep)         # (the wgrad of proj_out then reads [O | mlp] as one [M, 5d] operand)
+        if pl.run_out:
+            ops.gemm(Rows.of(cat2), self.W(f"{p}.proj_out.weight"), self.W(f"{p}.proj_out.bias"), Xa, d, 5 * d,
+                     EPI_BIAS_GATE_RES, gate=m[:, 2 * d:3 * d], gate_ld=3 * d, aux=pl.y_attn)
         return m
 
     def _embed(self, w, hidden_states, encoder_hidden_states):
@@ -703,12 +676,8 @@ class FluxTransformer2DModel(torch.nn.Module):
         N_pad = self._pad_kv_rows(B, L, N) if collect is None else None
         if N_pad is not None:
             hs, ids = self._padded_inputs(hidden_states, img_ids, N_pad)
-            w = self._workspace(B, L, N_pad)
-            w.kv_len = L + N
-            try:
-                out = self._forward_nograd_on(w, hs, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections, ids, None)
-            finally:
-                w.kv_len = None
+            out = self._forward_nograd_on(self._workspace(B, L, N_pad, kv_len=L + N), hs, encoder_hidden_states, timestep, guidance,
+                                          txt_ids, pooled_projections, ids, None)
             self.last_route = "padded_kv"
             self.padded_kv_calls += 1
             return out[:, :N].contiguous()
@@ -718,19 +687,21 @@ class FluxTransformer2DModel(torch.nn.Module):
 
     def _forward_nograd_on(self, w, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections,
                            img_ids, collect):
+        from .flux_backward import _BlockPlan
         B, L = w.B, w.L
+        double, single = _BlockPlan(w, True), _BlockPlan(w, False)      # nothing is kept: one plan per block type
         self._embed(w, hidden_states, encoder_hidden_states)
         temb, st = self._temb(B, timestep.to(self.store.device), guidance, pooled_projections)
         cos, sin = self._rope(txt_ids, img_ids)
         if collect is not None:
             collect.update(temb=temb.clone(), x_embed=w.X[:, L:].clone(), ctx_embed=w.X[:, :L].clone())
         for i in range(self.cfg.num_layers):
-            self._double_block(i, w, st, cos, sin)
+            self._double_block(i, w, st, cos, sin, double)
             if collect is not None:
                 collect[f"double{i}_h"] = w.X[:, L:].clone()
                 collect[f"double{i}_c"] = w.X[:, :L].clone()
         for i in range(self.cfg.num_single_layers):
-            self._single_block(i, w, st, cos, sin)
+            self._single_block(i, w, st, cos, sin, single)
             if collect is not None:
                 collect[f"single{i}_x"] = w.X.clone()
         out, _ = self._head(w, st)

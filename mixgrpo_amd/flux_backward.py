@@ -157,6 +157,54 @@ class _TrainView:
         self.dCt, self.At, self.Wt, self.ones = base.dCt, base.At, base.Wt, base.ones
 
 
+class _BlockPlan:
+    """One pass through one block: the tensor every role uses and which steps run.  Built here and nowhere else; the block
+    functions (`flux._double_block` / `_single_block`) and `_backward` read it and choose no buffer themselves.
+
+    The passes:  `_BlockPlan(w, double)` -- no-grad: nothing is kept, every step runs, scratch buffers of the workspace `w`;
+    `tr` (a `_Train` / `_TrainView`) and `blk` -- the training forward into the block's keep buffers `tr.keep[blk]` (without
+    keep buffers, MGX_KEEP_ACTS=0, it IS the no-grad pass); `recompute=True` -- the backward's recompute pass into `tr.save`:
+    in full from the saved block input, or, with keep buffers, a replay that reads them back and skips what made them.
+
+    Steps: `fused_qkv` (the no-grad projection with QK-norm / RoPE / V^T in its epilogue; otherwise `run_qkv` says whether
+    the GEMM in front of `qk_norm_rope` runs), `run_attn`, `run_out` (the projections that END a residual branch: to_out and
+    ff.net.2, proj_out), `run_ff` (ff.net.0 / proj_mlp).  `lean`: a single block's replay with the pre-activation kept builds
+    no [O | mlp] operand -- the backward reads O from its keep buffer at row stride d and forms gelu(hid_pre) in a transpose.
+
+    Roles: `restore` (block input to copy into the residual stream first, or None), `x_in` (input of the first LayerNorm),
+    `nrm1` / `nrm2`, `qkv`, `V` / `Qt` / `Kt` (extra outputs of `qk_norm_rope` for the attention backward, or None), `O` and
+    its row stride `ldo`, `lse`, `y_attn` and `hid_pre` (aux outputs of their GEMMs in the pass that runs them, what the
+    backward reads after a recompute), for double blocks `y_ff` and `x_mid`, for single blocks `O_keep` (the keep buffer that
+    `w.cat[:, :, :d]` is copied to by the forward and, unless lean, back from by the replay)."""
+
+    def __init__(self, w, double, tr=None, blk=None, recompute=False):
+        k = tr.keep[blk] if tr is not None and tr.keep else None
+        s = tr.save if recompute else {}
+        replay = recompute and k is not None
+        has = lambda name: k is not None and name in k
+        # a role's buffer: the block's keep buffer, else the recompute pass's save buffer, else the workspace's scratch (or none)
+        pick = lambda name, scratch=None: k[name] if has(name) else s.get(name, scratch)
+        d = w.X.shape[-1]
+        self.fused_qkv = k is None and not recompute
+        self.run_qkv = not (replay and has("qkv"))
+        self.run_attn = self.run_out = not replay
+        self.run_ff = not (replay and has("hid_pre"))
+        self.lean = not double and not self.run_ff
+        self.restore = tr.block_in[blk] if recompute and not replay else None
+        self.x_in = tr.block_in[blk] if replay else w.X
+        self.nrm1, self.nrm2 = s.get("nrm1", w.nrm), s.get("nrm2", w.nrm)
+        self.qkv = pick("qkv", w.qkv)
+        self.V, self.Qt, self.Kt = s.get("V"), s.get("Qt"), s.get("Kt")
+        self.lse = pick("lse", w.lse if recompute else None)
+        self.y_attn, self.hid_pre = pick("y_attn"), pick("hid_pre")
+        if double:
+            self.O, self.ldo = pick("O", w.O), d
+            self.y_ff, self.x_mid = pick("y_ff"), pick("x_mid")
+        else:
+            self.O_keep = pick("O")
+            self.O, self.ldo = (self.O_keep, d) if self.lean else (w.cat, 5 * d)
+
+
 def _train_buffers(cfg, w, device):
     """`_Train` view for the workspace view `w`; the base grows to the largest training batch seen."""
     base = w.train
@@ -177,35 +225,28 @@ class FluxFunction(torch.autograd.Function):
         B, N, _ = hidden_states.shape
         L = encoder_hidden_states.shape[1]
         # ops.ATTN_PAD_KV: a sequence off 256 runs on the workspace of the next multiple, zero image rows appended, the rows
-        # >= kv_len masked in the attention forward (model._attn) and backward (_attn_bwd); kv_len is set on the workspace for
-        # the length of this call and of the backward only
+        # >= kv_len masked in the attention forward (model._attn) and backward (_attn_bwd); the workspace view of this call
+        # carries kv_len, and serves the backward
         N_pad = model._pad_kv_rows_train(B, L, N)
         kv_len = None
         if N_pad is not None:
             hidden_states, img_ids = model._padded_inputs(hidden_states, img_ids, N_pad)
             kv_len = L + N
-        w = model._workspace(B, L, N if N_pad is None else N_pad)
+        w = model._workspace(B, L, N if N_pad is None else N_pad, kv_len=kv_len)
         tr = _train_buffers(cfg, w, model.store.device)
-        w.kv_len = kv_len
-        try:
-            ehs = model._embed(w, hidden_states, encoder_hidden_states)
-            keep = {}
-            temb, st = model._temb(B, timestep.to(model.store.device), guidance, pooled_projections, keep=keep)
-            cos, sin = model._rope(txt_ids, img_ids)
-            mods = []
-            blk = 0
-            for i in range(cfg.num_layers):
-                tr.block_in[blk].copy_(w.X)
-                mods.append(model._double_block(i, w, st, cos, sin, keep=tr.keep[blk] if tr.keep else None))
-                blk += 1
-            for i in range(cfg.num_single_layers):
-                tr.block_in[blk].copy_(w.X)
-                mods.append(model._single_block(i, w, st, cos, sin, keep=tr.keep[blk] if tr.keep else None))
-                blk += 1
-            tr.x_final.copy_(w.X)
-            out, e = model._head(w, st)
-        finally:
-            w.kv_len = None
+        ehs = model._embed(w, hidden_states, encoder_hidden_states)
+        keep = {}
+        temb, st = model._temb(B, timestep.to(model.store.device), guidance, pooled_projections, keep=keep)
+        cos, sin = model._rope(txt_ids, img_ids)
+        mods = []
+        for blk in range(cfg.num_layers + cfg.num_single_layers):
+            tr.block_in[blk].copy_(w.X)
+            if blk < cfg.num_layers:
+                mods.append(model._double_block(blk, w, st, cos, sin, _BlockPlan(w, True, tr, blk)))
+            else:
+                mods.append(model._single_block(blk - cfg.num_layers, w, st, cos, sin, _BlockPlan(w, False, tr, blk)))
+        tr.x_final.copy_(w.X)
+        out, e = model._head(w, st)
         model.last_train_route = "plain" if kv_len is None else "padded_kv"
         model.padded_kv_train_calls += int(kv_len is not None)
         # the saved activations live in the model's shared per-shape workspace: ONE pending backward per model at a time
@@ -214,7 +255,7 @@ class FluxFunction(torch.autograd.Function):
         w.train.generation = getattr(w.train, "generation", 0) + 1
         ctx.generation = w.train.generation
         ctx.model, ctx.w, ctx.tr = model, w, tr
-        ctx.kv_len, ctx.rows = kv_len, N
+        ctx.rows = N
         ctx.saved = dict(ehs=ehs, in16=w.in16.clone(), temb=temb, st=st, keep=keep, cos=cos, sin=sin, mods=mods, e=e)
         return out if kv_len is None else out[:, :N].contiguous()
 
@@ -226,17 +267,11 @@ class FluxFunction(torch.autograd.Function):
                            "grad-enabled forward of the same model (one pending backward per model; call backward() "
                            "before the next training forward)")
         dout = dout.contiguous().to(BF16)
-        if ctx.kv_len is None:
-            _backward(ctx.model, ctx.w, ctx.tr, ctx.saved, dout)
-            return (None,) * 9
-        # padded: the padding tokens' rows of dout are zero, and stay zero in every gradient behind them
-        pad = dout.new_zeros(dout.shape[0], ctx.w.N, dout.shape[2])
-        pad[:, :ctx.rows] = dout
-        ctx.w.kv_len = ctx.kv_len
-        try:
-            _backward(ctx.model, ctx.w, ctx.tr, ctx.saved, pad)
-        finally:
-            ctx.w.kv_len = None
+        if ctx.w.kv_len is not None:
+            # padded: the padding tokens' rows of dout are zero, and stay zero in every gradient behind them
+            dout, valid = dout.new_zeros(dout.shape[0], ctx.w.N, dout.shape[2]), dout
+            dout[:, :ctx.rows] = valid
+        _backward(ctx.model, ctx.w, ctx.tr, ctx.saved, dout)
         return (None,) * 9
 
 
@@ -307,9 +342,6 @@ def _backward(model, w, tr, sv, dout):
     store = model.store
     g32 = store.ensure_grad()
     dst = torch.zeros(B, d, dtype=BF16, device=dev)        # grad wrt st = silu(temb), summed over all users
-    save0 = tr.save
-    save = save0
-    row0 = {"txt": 0, "img": B * L}
 
     def srows(t, which, width):
         return model._stream_rows(t, w, which, width)
@@ -317,7 +349,7 @@ def _backward(model, w, tr, sv, dout):
     # ---------------- head: out = proj_out( LN(x_img) * (1+scale) + shift )
     cout = cfg.patch_size * cfg.patch_size * cfg.in_channels
     e = sv["e"]
-    nrm = save["nrm1"][:B * N]
+    nrm = tr.save["nrm1"][:B * N]
     ops.ln_modulate(srows(tr.x_final, "img", d), e[:, d:2 * d], e[:, 0:d], 2 * d, nrm, d)
     dC = Rows.of(dout.view(B * N, cout))
     _wgrad(model, tr, Rows.of(nrm), d, dC, cout, "proj_out.weight", "proj_out.bias")
@@ -339,111 +371,83 @@ def _backward(model, w, tr, sv, dout):
         blk = cfg.num_layers + i
         p = f"single_transformer_blocks.{i}"
         m = sv["mods"][blk]
-        kept = tr.keep[blk] if tr.keep else None
-        save = dict(save0, y_attn=kept["y_attn"]) if kept else save0
-        if kept and "hid_pre" in kept:
-            save["hid_pre"] = kept["hid_pre"]                   # kept by the forward: the replay skips proj_mlp
-        if kept is None:
-            w.X.copy_(tr.block_in[blk])                        # full recompute rewrites the residual stream
-        model._single_block(i, w, st_, cos, sin, save=save, mod_in=m, keep=kept, replay=kept is not None,
-                            x_in=tr.block_in[blk] if kept is not None else None)
-        lse_b = kept["lse"] if kept is not None else w.lse
+        pl = _BlockPlan(w, False, tr, blk, recompute=True)
+        model._single_block(i, w, st_, cos, sin, pl, mod_in=m)
         dmod = torch.empty(B, 3 * d, dtype=BF16, device=dev)
         x_in = Rows(tr.block_in[blk], M, d, S, S * d)
         dXr = Rows(tr.dX, M, d, S, S * d)
-        cat2 = w.cat.view(M, 5 * d)
-        # everything kept (attention output AND the FF pre-activation): the recompute pass built no [O | mlp] operand -- the
-        # weight gradient of proj_out takes O from its keep buffer and gelu(hid_pre) formed inside the transpose, and the
-        # attention backward reads O / writes dO at row stride d
-        lean = kept is not None and "hid_pre" in kept
         # out = x + gate * y ; y = proj_out(cat)
-        ops.gate_bwd(dXr, save["y_attn"], m[:, 2 * d:3 * d], 3 * d, tr.dy, dmod[:, 2 * d:3 * d], B, S, d)
+        ops.gate_bwd(dXr, pl.y_attn, m[:, 2 * d:3 * d], 3 * d, tr.dy, dmod[:, 2 * d:3 * d], B, S, d)
         dyr = Rows.of(tr.dy)
-        a_op = [(Rows.of(kept["O"].view(M, d)), d, False), (Rows.of(kept["hid_pre"]), 4 * d, True)] if lean else Rows.of(cat2)
+        # lean (attention output AND the FF pre-activation kept): the recompute pass built no [O | mlp] operand -- the weight
+        # gradient of proj_out takes O from its keep buffer and gelu(hid_pre) formed inside the transpose, and the attention
+        # backward reads O / writes dO at row stride d instead of 5d
+        a_op = [(Rows.of(pl.O.view(M, d)), d, False), (Rows.of(pl.hid_pre), 4 * d, True)] if pl.lean else Rows.of(pl.O.view(M, 5 * d))
         _wgrad(model, tr, a_op, 5 * d, dyr, d, f"{p}.proj_out.weight", f"{p}.proj_out.bias")
-        dcat = tr.dO.view(M, 5 * d)
-        dO1 = tr.dO.view(-1)[:M * d].view(B, S, d)             # lean: dO alone, [B, S, d]
+        dO = tr.dO.view(-1)[:M * pl.ldo].view(B, S, pl.ldo)    # d(cat) [B, S, 5d]; lean: dO alone, [B, S, d]
         dbig = tr.dbig                                         # [M, 7d] = [dq | dk | dv | dmlp_pre]
         # d(cat)[:, :d] = dO (attention output grad) ; d(cat)[:, d:] -> through GELU -> dbig[:, 3d:]
         stW = store.view(store.w16, f"{p}.proj_out.weight")
         Wt = tr.Wt[:5 * d * d].view(5 * d, d)
         ops.transpose(Rows.of(stW), 5 * d, Wt, d)
-        ops.gemm(dyr, Wt[0:d], None, Rows.of(dO1.view(M, d)) if lean else Rows(dcat, M, 5 * d), d, d, EPI_BIAS)
-        ops.gemm(dyr, Wt[d:5 * d], None, Rows(dbig[0, 3 * d:], M, 7 * d), 4 * d, d, EPI_DGELU, aux=save["hid_pre"],
-                 ldaux=4 * d)
-        if lean:
-            _attn_bwd(w, w.Q, w.K, save["V"], save["Qt"], save["Kt"], kept["O"], dO1, lse_b, tr, B, H, S, Sp, d, S * d, scale)
-        else:
-            _attn_bwd(w, w.Q, w.K, save["V"], save["Qt"], save["Kt"], w.cat, tr.dO, lse_b, tr, B, H, S, Sp, 5 * d, S * 5 * d, scale)
+        ops.gemm(dyr, Wt[0:d], None, Rows.of(dO.view(M, pl.ldo)), d, d, EPI_BIAS)
+        ops.gemm(dyr, Wt[d:5 * d], None, Rows(dbig[0, 3 * d:], M, 7 * d), 4 * d, d, EPI_DGELU, aux=pl.hid_pre, ldaux=4 * d)
+        _attn_bwd(w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO, pl.lse, tr, B, H, S, Sp, pl.ldo, S * pl.ldo, scale)
         # qk norm / rope backward writes [dq|dk|dv] straight into columns 0..3d of the [M, 7d] staging matrix
-        qkv_b = kept["qkv"] if kept is not None and "qkv" in kept else w.qkv
-        ops.qk_norm_rope_bwd(qkv_b, model.W32(f"{p}.attn.norm_q.weight"), model.W32(f"{p}.attn.norm_k.weight"), cos, sin,
+        ops.qk_norm_rope_bwd(pl.qkv, model.W32(f"{p}.attn.norm_q.weight"), model.W32(f"{p}.attn.norm_k.weight"), cos, sin,
                              tr.dQ, tr.dK, tr.dV, dbig, store.view(g32, f"{p}.attn.norm_q.weight"),
                              store.view(g32, f"{p}.attn.norm_k.weight"), B, H, S, Sp, S, 0, ld_dqkv=7 * d, q_scale=q_scale)
         dbr = Rows.of(dbig)
-        _wgrad(model, tr, Rows.of(save["nrm1"]), d, dbr, 7 * d, f"{p}.attn.to_q.weight", f"{p}.attn.to_q.bias", rows=True)
+        _wgrad(model, tr, Rows.of(pl.nrm1), d, dbr, 7 * d, f"{p}.attn.to_q.weight", f"{p}.attn.to_q.bias", rows=True)
         _dgrad(model, tr, dbr, 7 * d, d, f"{p}.attn.to_q.weight", Rows.of(tr.dnrm), rows=True)
         ops.ln_modulate_bwd(tr.dnrm, x_in, m[:, d:2 * d], 3 * d, dXr, True, dmod[:, 0:d], dmod[:, d:2 * d], d)
         _skinny_bwd(model, tr, dmod, st_, f"{p}.norm.linear.weight", f"{p}.norm.linear.bias", 3 * d, d, dst)
         grad_ready(p)
 
     # ---------------- double blocks (reverse)
-    # text stream first (its rows come first in every stacked buffer)
-    streams = (("txt", "norm1_context", ("add_q_proj", "add_k_proj", "add_v_proj"), "norm_added_q", "norm_added_k",
-                "to_add_out", "ff_context", L, 0),
-               ("img", "norm1", ("to_q", "to_k", "to_v"), "norm_q", "norm_k", "to_out.0", "ff", N, L))
-    sl = {"txt": slice(0, B * L), "img": slice(B * L, B * S)}
+    streams, sl = model._streams(w)
     dO3 = tr.dO.view(-1)[:B * S * d].view(B, S, d)
     dh_all = tr.dbig.view(-1)[:M * 4 * d].view(M, 4 * d)
     dqkv_all = tr.dbig.view(-1)[:M * 3 * d].view(M, 3 * d)
     for i in reversed(range(cfg.num_layers)):
         p = f"transformer_blocks.{i}"
         mods = sv["mods"][i]
-        kept = tr.keep[i] if tr.keep else None
-        save = dict(save0, y_attn=kept["y_attn"], y_ff=kept["y_ff"], x_mid=kept["x_mid"]) if kept else save0
-        if kept and "hid_pre" in kept:
-            save["hid_pre"] = kept["hid_pre"]                   # kept by the forward: the replay skips ff.net.0
-        if kept is None:
-            w.X.copy_(tr.block_in[i])                          # full recompute rewrites the residual stream
-        model._double_block(i, w, st_, cos, sin, save=save, mods_in=mods, keep=kept, replay=kept is not None,
-                            x_in=tr.block_in[i] if kept is not None else None)
-        O_b, lse_b = (kept["O"], kept["lse"]) if kept is not None else (w.O, w.lse)
+        pl = _BlockPlan(w, True, tr, i, recompute=True)
+        model._double_block(i, w, st_, cos, sin, pl, mods_in=mods)
         dmods = {k: torch.empty(B, 6 * d, dtype=BF16, device=dev) for k in ("img", "txt")}
         # ---- FF branch: out = x_mid + gate_mlp * ff2(gelu(ff1(LNmod(x_mid))))
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             m, dm = mods[name], dmods[name]
-            ops.gate_bwd(srows(tr.dX, name, d), save["y_ff"][sl[name]], m[:, 5 * d:6 * d], 6 * d, tr.dy[sl[name]],
+            ops.gate_bwd(srows(tr.dX, name, d), pl.y_ff[sl[name]], m[:, 5 * d:6 * d], 6 * d, tr.dy[sl[name]],
                          dm[:, 5 * d:6 * d], B, rows, d)
-            # (FF pre-activation kept: the recompute pass formed no activation; gelu(hid_pre) is applied inside the transpose)
-            a_op = [(Rows.of(kept["hid_pre"][sl[name]]), 4 * d, True)] if kept is not None and "hid_pre" in kept \
-                else Rows.of(w.hid[sl[name]])
+            # (ff.net.0 not run again: the recompute pass formed no activation; gelu(hid_pre) is applied inside the transpose)
+            a_op = Rows.of(w.hid[sl[name]]) if pl.run_ff else [(Rows.of(pl.hid_pre[sl[name]]), 4 * d, True)]
             _wgrad(model, tr, a_op, 4 * d, Rows.of(tr.dy[sl[name]]), d, f"{p}.{ffn}.net.2.weight", f"{p}.{ffn}.net.2.bias")
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             _dgrad(model, tr, Rows.of(tr.dy[sl[name]]), d, 4 * d, f"{p}.{ffn}.net.2.weight", Rows.of(dh_all[sl[name]]),
-                   epi=EPI_DGELU, aux=save["hid_pre"][sl[name]], ldaux=4 * d)
+                   epi=EPI_DGELU, aux=pl.hid_pre[sl[name]], ldaux=4 * d)
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            _wgrad(model, tr, Rows.of(save["nrm2"][sl[name]]), d, Rows.of(dh_all[sl[name]]), 4 * d, f"{p}.{ffn}.net.0.proj.weight",
+            _wgrad(model, tr, Rows.of(pl.nrm2[sl[name]]), d, Rows.of(dh_all[sl[name]]), 4 * d, f"{p}.{ffn}.net.0.proj.weight",
                    f"{p}.{ffn}.net.0.proj.bias")
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             _dgrad(model, tr, Rows.of(dh_all[sl[name]]), 4 * d, d, f"{p}.{ffn}.net.0.proj.weight", Rows.of(tr.dnrm[sl[name]]))
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             m, dm = mods[name], dmods[name]
             dXs = srows(tr.dX, name, d)
-            ops.ln_modulate_bwd(tr.dnrm[sl[name]], srows(save["x_mid"], name, d), m[:, 4 * d:5 * d], 6 * d, dXs, True,
+            ops.ln_modulate_bwd(tr.dnrm[sl[name]], srows(pl.x_mid, name, d), m[:, 4 * d:5 * d], 6 * d, dXs, True,
                                 dm[:, 3 * d:4 * d], dm[:, 4 * d:5 * d], d)
             # ---- attention branch: x_mid = x_in + gate_msa * to_out(O)
-            ops.gate_bwd(dXs, save["y_attn"][sl[name]], m[:, 2 * d:3 * d], 6 * d, tr.dy[sl[name]], dm[:, 2 * d:3 * d], B, rows, d)
-            _wgrad(model, tr, srows(O_b, name, d), d, Rows.of(tr.dy[sl[name]]), d, f"{p}.attn.{outn}.weight",
+            ops.gate_bwd(dXs, pl.y_attn[sl[name]], m[:, 2 * d:3 * d], 6 * d, tr.dy[sl[name]], dm[:, 2 * d:3 * d], B, rows, d)
+            _wgrad(model, tr, srows(pl.O, name, d), d, Rows.of(tr.dy[sl[name]]), d, f"{p}.attn.{outn}.weight",
                    f"{p}.attn.{outn}.bias")
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             _dgrad(model, tr, Rows.of(tr.dy[sl[name]]), d, d, f"{p}.attn.{outn}.weight", srows(dO3, name, d))
-        _attn_bwd(w, w.Q, w.K, save["V"], save["Qt"], save["Kt"], O_b, dO3, lse_b, tr, B, H, S, Sp, d, S * d, scale)
-        qkv_b = kept["qkv"] if kept is not None and "qkv" in kept else w.qkv
+        _attn_bwd(w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO3, pl.lse, tr, B, H, S, Sp, d, S * d, scale)
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            ops.qk_norm_rope_bwd(qkv_b[sl[name]], model.W32(f"{p}.attn.{nq}.weight"), model.W32(f"{p}.attn.{nk}.weight"), cos,
+            ops.qk_norm_rope_bwd(pl.qkv[sl[name]], model.W32(f"{p}.attn.{nq}.weight"), model.W32(f"{p}.attn.{nk}.weight"), cos,
                                  sin, tr.dQ, tr.dK, tr.dV, dqkv_all[sl[name]], store.view(g32, f"{p}.attn.{nq}.weight"),
                                  store.view(g32, f"{p}.attn.{nk}.weight"), B, H, S, Sp, rows, s0, q_scale=q_scale)
-            _wgrad(model, tr, Rows.of(save["nrm1"][sl[name]]), d, Rows.of(dqkv_all[sl[name]]), 3 * d, f"{p}.attn.{qkvn[0]}.weight",
+            _wgrad(model, tr, Rows.of(pl.nrm1[sl[name]]), d, Rows.of(dqkv_all[sl[name]]), 3 * d, f"{p}.attn.{qkvn[0]}.weight",
                    f"{p}.attn.{qkvn[0]}.bias", rows=True)
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             _dgrad(model, tr, Rows.of(dqkv_all[sl[name]]), 3 * d, d, f"{p}.attn.{qkvn[0]}.weight", Rows.of(tr.dnrm[sl[name]]),

@@ -32,17 +32,34 @@ def gemm(A: Rows, W, bias, C: Rows, N, K, epi=EPI_BIAS, gate=None, gate_ld=0, au
     """C = epi(A @ W[N,K]^T + bias).  `aux`: plain [M, ldaux] matrix (ldaux defaults to N); pass a tensor whose
     data_ptr() is its first element."""
     assert A.M == C.M
-    if GEMM_PROFILE is not None:     # bench.py: HIP events around every GEMM launch on the launch stream
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _gemm_launch(A, W, bias, C, N, K, epi, gate, gate_ld, aux, beta, ldw, ldaux)
-        e1.record()
-        GEMM_PROFILE.append((e0, e1, 2.0 * A.M * N * K, (A.M, N, K, epi)))
-        return
-    _gemm_launch(A, W, bias, C, N, K, epi, gate, gate_ld, aux, beta, ldw, ldaux)
+    _profiled(_gemm_launch, (A, W, bias, C, N, K, epi, gate, gate_ld, aux, beta, ldw, ldaux), 2.0 * A.M * N * K, (A.M, N, K, epi))
 
 
 GEMM_PROFILE = None
+
+
+def _profiled(launch, args, flops, shape):
+    """`launch(*args)`, and while bench.py holds a list in GEMM_PROFILE: HIP events around it on the launch stream, appended as
+    (e0, e1, flops, (M, N, K, epi)).  A refused launch (`_try` said False) appends nothing."""
+    if GEMM_PROFILE is None:
+        return launch(*args)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    took = launch(*args)
+    if took is not False:
+        e1.record()
+        GEMM_PROFILE.append((e0, e1, flops, shape))
+    return took
+
+
+def _try(entry, *args):
+    """Call an entry point that may refuse its problem: False for rc 1 (refused, nothing launched), True after a launch; any
+    other code raises."""
+    rc = entry(*args)
+    if rc == 1:
+        return False
+    check(rc)
+    return True
 
 # MGX_LINEAR_VT=0: the value projection always leaves row-major and mgx_qk_norm_rope_fwd transposes it (the training passes
 # do that anyway: their backward needs V row-major as well)
@@ -57,19 +74,9 @@ def linear_t(X, W, bias, Ct, tokens, F, K, ld_ct, tok_rpb, ct_bstride):
     token-contiguous).  X plain [tokens, K], W [F, K]; Ct: a tensor whose data_ptr() is the element of (b 0, f 0, t 0).
     False -- nothing launched -- when the persistent kernel cannot take the shape."""
     ws = _sk_workspace(X.device) if GEMM_STREAM_K else None
-    prof = GEMM_PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = lib().mgx_linear_bf16_t(ptr(X), ptr(W), ptr(bias), Ct.data_ptr(), tokens, F, K, K, K, ld_ct, tok_rpb, ct_bstride,
-                                 None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), stream())
-    if rc == 1:
-        return False
-    check(rc)
-    if prof:
-        e1.record()
-        GEMM_PROFILE.append((e0, e1, 2.0 * tokens * F * K, (F, tokens, K, EPI_BIAS)))
-    return True
+    return _profiled(_try, (lib().mgx_linear_bf16_t, ptr(X), ptr(W), ptr(bias), Ct.data_ptr(), tokens, F, K, K, K, ld_ct, tok_rpb,
+                            ct_bstride, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), stream()),
+                     2.0 * tokens * F * K, (F, tokens, K, EPI_BIAS))
 
 
 def _gemm_launch(A, W, bias, C, N, K, epi, gate, gate_ld, aux, beta, ldw, ldaux):
@@ -171,19 +178,9 @@ def linear_qk_norm_rope(X, Wqk, bias, wq, wk, cos, sin, Q, K, B, H, S, rows_per_
     split run in the GEMM's epilogue).  X plain [B * rows_per_batch, Kdim], Wqk [2 * H * 128, Kdim].  False -- nothing launched --
     when the persistent kernel cannot take the problem: the caller keeps `gemm` + `qk_norm_rope`.  `pairs`: [S, 64, 2] (cos, sin)
     per rotation pair when both entries of every pair of `cos` / `sin` are equal (`rope_pair_table`): half the table bytes."""
-    prof = GEMM_PROFILE is not None
-    if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = lib().mgx_linear_qk_norm_rope(ptr(X), ptr(Wqk), ptr(bias), ptr(wq), ptr(wk), ptr(cos), ptr(sin), ptr(pairs), ptr(Q), ptr(K),
-                                       B, H, S, rows_per_batch, s0, Kdim, Kdim, Kdim, float(q_scale), stream())
-    if rc == 1:
-        return False
-    check(rc)
-    if prof:
-        e1.record()
-        GEMM_PROFILE.append((e0, e1, 2.0 * B * rows_per_batch * 2 * H * 128 * Kdim, (B * rows_per_batch, 2 * H * 128, Kdim, 5)))
-    return True
+    return _profiled(_try, (lib().mgx_linear_qk_norm_rope, ptr(X), ptr(Wqk), ptr(bias), ptr(wq), ptr(wk), ptr(cos), ptr(sin), ptr(pairs),
+                            ptr(Q), ptr(K), B, H, S, rows_per_batch, s0, Kdim, Kdim, Kdim, float(q_scale), stream()),
+                     2.0 * B * rows_per_batch * 2 * H * 128 * Kdim, (B * rows_per_batch, 2 * H * 128, Kdim, 5))
 
 
 def rope_pair_table(cos, sin):
@@ -221,12 +218,8 @@ ATTN_PAD_KV = os.environ.get("MGX_ATTN_PAD_KV", "0") != "0"
 def attn_fwd_log2_kv(Q2, K, Vt, O_ptr_tensor, lse, B, H, Sa, kv_len, ldo, o_bstride):
     """attn_fwd_log2 on operands allocated at Sa (% 256 == 0) with the keys >= kv_len masked (`mgx_attn_fwd_log2_kv`).  False --
     nothing launched -- when the 64-query kernel cannot take the problem (attn_fwd_kv_path): the caller keeps the unpadded path."""
-    rc = lib().mgx_attn_fwd_log2_kv(ptr(Q2), ptr(K), ptr(Vt), O_ptr_tensor.data_ptr(), ptr(lse), B, H, Sa, kv_len, ldo, o_bstride,
-                                    stream())
-    if rc == 1:
-        return False
-    check(rc)
-    return True
+    return _try(lib().mgx_attn_fwd_log2_kv, ptr(Q2), ptr(K), ptr(Vt), O_ptr_tensor.data_ptr(), ptr(lse), B, H, Sa, kv_len, ldo, o_bstride,
+                stream())
 
 
 def attn_fwd_kv_path(B, H, Sa, kv_len, ldo, o_bstride):
@@ -327,12 +320,8 @@ def attn_bwd_kv(Q, K, V, Qt, Kt, O, dO, lse, delta, dOt, dQ, dK, dV, B, H, Sa, k
     """attn_bwd on operands allocated at Sa (% 256 == 0) with the keys and queries >= kv_len masked and the rows >= kv_len of
     dQ / dK / dV written as zero (`mgx_attn_bwd_kv`).  False -- nothing launched -- when the 64-wide pair cannot take the
     problem (attn_bwd_kv_path): there is no other kernel behind it."""
-    rc = lib().mgx_attn_bwd_kv(ptr(Q), ptr(K), ptr(V), ptr(Qt), ptr(Kt), O.data_ptr(), dO.data_ptr(), ptr(lse), ptr(delta),
-                               ptr(dOt), ptr(dQ), ptr(dK), ptr(dV), B, H, Sa, kv_len, ldo, o_bstride, scale, stream())
-    if rc == 1:
-        return False
-    check(rc)
-    return True
+    return _try(lib().mgx_attn_bwd_kv, ptr(Q), ptr(K), ptr(V), ptr(Qt), ptr(Kt), O.data_ptr(), dO.data_ptr(), ptr(lse), ptr(delta),
+                ptr(dOt), ptr(dQ), ptr(dK), ptr(dV), B, H, Sa, kv_len, ldo, o_bstride, scale, stream())
 
 
 def attn_bwd_kv_path(B, H, Sa, kv_len, ldo, o_bstride):

@@ -296,6 +296,40 @@ def test_selective_saving_is_bit_identical_to_full_recompute(monkeypatch):
         assert torch.equal(grads[0][1], other[1])
 
 
+@pytest.mark.parametrize("keep,keep_ff,keep_qkv,gelu,gate_res,attn", [
+    (False, "0", "0", 2 * 2 + 2, 4 * 2 + 2, 4),      # full recompute: every block's ff.net.0 / proj_mlp, to_out / ff.net.2 / proj_out, attention
+    (True, "0", "0", 2 * 2 + 2, 0, 0),               # kept O / lse / y_attn / y_ff / x_mid: only the up-projections run again
+    (True, "99", "99", 0, 0, 0)])                    # everything kept: the recompute pass runs no GEMM and no attention
+def test_recompute_pass_runs_only_what_was_not_kept(monkeypatch, keep, keep_ff, keep_qkv, gelu, gate_res, attn):
+    """What `backward()` launches again of the forward at 2 + 2 blocks, counted per GEMM epilogue (the backward's own GEMMs
+    are EPI_BIAS / EPI_DGELU / EPI_F32_ACC) and per attention forward."""
+    from mixgrpo_amd import flux_backward as FB
+    from mixgrpo_amd import ops
+    from mixgrpo_amd.flux import FluxTransformer2DModel
+    monkeypatch.setattr(FB, "KEEP_ACTS", keep)
+    monkeypatch.setattr(FB, "KEEP_FF", keep_ff)
+    monkeypatch.setattr(FB, "KEEP_QKV", keep_qkv)
+    ocfg, P, m = build_pair(small_cfg(2, 2))
+    x, ehs, pooled, ids, tids, t, gd = make_inputs(2, 6, 10, 24, seed=3)
+    m.train()
+    out = m(x.cuda(), ehs.cuda(), t.cuda(), gd.cuda(), tids.cuda(), pooled.cuda(), ids.cuda())[0]
+    counts = {"attn": 0}
+    gemm, attn_fwd = ops.gemm, FluxTransformer2DModel._attn
+
+    def counted_gemm(A, W, bias, C, N, K, epi=ops.EPI_BIAS, **kw):
+        counts[epi] = counts.get(epi, 0) + 1
+        return gemm(A, W, bias, C, N, K, epi, **kw)
+
+    def counted_attn(self, *a, **kw):
+        counts["attn"] += 1
+        return attn_fwd(self, *a, **kw)
+
+    monkeypatch.setattr(ops, "gemm", counted_gemm)
+    monkeypatch.setattr(FluxTransformer2DModel, "_attn", counted_attn)
+    out.float().sum().backward()
+    assert (counts.get(ops.EPI_BIAS_GELU, 0), counts.get(ops.EPI_BIAS_GATE_RES, 0), counts["attn"]) == (gelu, gate_res, attn), counts
+
+
 def test_attention_backward_vs_torch():
     from mixgrpo_amd import ops
     B, H, S = 1, 2, 700
