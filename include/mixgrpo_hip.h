@@ -290,7 +290,7 @@ int mgx_attn_fwd_kv_path(int B, int H, int Sa, int kv_len, long ldo, long o_bstr
  * [B,H,S,128] = e4m3(x * 448 / amax), V8t [B,H,128,Sp] likewise with the keys of every 64-key block in the order
  * p = 32h + 16kb + i  <-  key 32kb + 8(i>>2) + 4h + (i&3)  (the order the kernel's P^T fragment holds them).
  * mgx_attn_fwd_fp8: O, lse as mgx_attn_fwd from the quantised operands (both contractions on e4m3 MFMA, P in e4m3,
- * fp32 statistics / accumulators).  The backward stays mgx_attn_bwd on the bf16 operands with this O / lse. */
+ * fp32 statistics / accumulators).  The backward is mgx_attn_bwd on the bf16 operands with this O / lse, or mgx_attn_bwd_fp8. */
 int mgx_attn_fp8_quantize(const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, uint8_t* Q8, uint8_t* K8,
                           uint8_t* V8t, float* amax, int B, int H, int S, int Sp, void* stream);
 int mgx_attn_fwd_fp8(const uint8_t* Q8, const uint8_t* K8, const uint8_t* V8t, const float* amax, uint16_t* O,
@@ -305,6 +305,24 @@ int mgx_attn_bwd(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const 
                  const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt, uint16_t* dQ,
                  uint16_t* dK, uint16_t* dV, int B, int H, int S, int Sp, long ldo, long o_bstride, float scale,
                  void* stream);
+
+/* Opt-in e4m3 backward of mgx_attn_fwd_fp8 (csrc/attention_fp8_bwd.hip): the straight-through gradient of the quantised
+ * forward.  The argument list and the meaning of `scale` are mgx_attn_bwd's (O, lse: what mgx_attn_fwd_fp8 wrote); dOt is
+ * filled by the same prep kernel, delta leaves as sum_d dO8 * O on the dequantised e4m3 dO (the dO that dP is formed from).  Q8, K8, V8 are requantised from the bf16 Q, K, V handed in (the forward's quantiser:
+ * same inputs, same bits), dO per (batch, head) like them; S is recomputed with the forward's instruction, so
+ * P = exp(S - lse) is the forward's probability.  All five products run on the scaled e4m3 MFMA: P enters dV as e4m3(256 P),
+ * dS = P (dP - delta) enters dK and dQ as MX blocks (32 contiguous values along the contraction dimension share a power-of-two
+ * scale).
+ * Any S >= 1; only rows < S of dQ, dK, dV [B,H,S,128] are written; the padding columns of Qt, Kt may hold anything.
+ * amax: float [4][B*H], written (Q, K, V, dO).  ws: mgx_attn_bwd_fp8_workspace(B, H, S, Sp) bytes, 16-byte aligned, ws_bytes its
+ * size; sections in order Q8, K8, V8, dO8 [B,H,S,128] e4m3 (each rounded up to a multiple of 256 bytes), then Q8t, K8t, dO8t
+ * [B,H,128,Sp]: transposed, zero from column S on, the columns of every 64-block in the order of V8t (mgx_attn_fp8_quantize).
+ * mgx_attn_bwd_fp8_workspace is host code (needs no GPU); -1 for sizes mgx_attn_bwd_fp8 refuses. */
+long mgx_attn_bwd_fp8_workspace(int B, int H, int S, int Sp);
+int mgx_attn_bwd_fp8(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* Qt, const uint16_t* Kt,
+                     const uint16_t* O, const uint16_t* dO, const float* lse, float* delta, uint16_t* dOt, uint16_t* dQ,
+                     uint16_t* dK, uint16_t* dV, uint8_t* ws, float* amax, int B, int H, int S, int Sp, long ldo,
+                     long o_bstride, float scale, long ws_bytes, void* stream);
 
 /* mgx_attn_bwd with a masked tail: the backward of mgx_attn_fwd_log2_kv (autograd of F.scaled_dot_product_attention,
  * fastvideo/train_grpo_flux.py:134-144, at a token count off 256), on the generated 64-wide pair and nothing else.

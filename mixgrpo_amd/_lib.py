@@ -81,6 +81,8 @@ SIGNATURES = {
     "mgx_attn_fp8_quantize": (_I, [_P] * 7 + [_I] * 4 + [_P]),
     "mgx_attn_fwd_fp8": (_I, [_P] * 6 + [_I] * 4 + [_L, _L, _F, _P]),
     "mgx_attn_bwd": (_I, [_P] * 13 + [_I] * 4 + [_L, _L, _F, _P]),
+    "mgx_attn_bwd_fp8_workspace": (_L, [_I] * 4),
+    "mgx_attn_bwd_fp8": (_I, [_P] * 15 + [_I] * 4 + [_L, _L, _F, _L, _P]),
     "mgx_attn_bwd_kv": (_I, [_P] * 13 + [_I] * 4 + [_L, _L, _F, _P]),
     "mgx_attn_bwd_kv_path": (_I, [_I] * 4 + [_L, _L]),
     "mgx_attn_kv_operands": (_I, [_I] * 3 + [C.POINTER(_I), _I]),

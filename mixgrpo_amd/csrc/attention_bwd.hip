@@ -11,6 +11,7 @@
 // global memory ([B,H,128,Sp]: Qt, Kt by qk_norm_rope, dOt by attn_bwd_prep), so every LDS fragment read is a
 // plain conflict-free ds_read (XOR-swizzled images), cf. the forward kernel.
 #include "../../include/mixgrpo_hip.h"
+#include "attn_fp8_quant.h"
 #include "attn_operands.h"
 #include "common.h"
 
@@ -590,6 +591,12 @@ static int attn_bwd_begin(BwdArgs& g, const uint16_t* Q, const uint16_t* K, cons
   g.kv_len = kv_len;
   attn_bwd_prep_kernel<<<dim3(Sp / 64, H, B), 256, 0, st>>>(O, dO, ldo, o_bstride, delta, dOt, H, S, Sp, kv_len);
   return MGX_OK;
+}
+
+// The prep of mgx_attn_bwd for the e4m3 backward (attention_fp8_bwd.hip): the same kernel, the same launch.
+void mgx_attn_bwd_prep_launch(const uint16_t* O, const uint16_t* dO, long ldo, long o_bstride, float* delta, uint16_t* dOt,
+                              int B, int H, int S, int Sp, hipStream_t st) {
+  attn_bwd_prep_kernel<<<dim3(Sp / 64, H, B), 256, 0, st>>>(O, dO, ldo, o_bstride, delta, dOt, H, S, Sp, S);
 }
 
 extern "C" int mgx_attn_bwd(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* Qt, const uint16_t* Kt,

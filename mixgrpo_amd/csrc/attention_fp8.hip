@@ -5,7 +5,7 @@
 // with Q, K, V quantised per (batch, head) to e4m3 (scale 448 / amax) and both contractions on
 // v_mfma_scale_f32_32x32x64_f8f6f4 (block scales fixed at 2^0): twice the bf16 MFMA rate at a quarter of the
 // instructions.  Softmax statistics, row sums, the O accumulator and the LSE stay fp32; P is quantised to e4m3 in
-// [0, 256].  The backward pass stays bf16 (mgx_attn_bwd with this kernel's O / LSE).
+// [0, 256].  The backward pass is bf16 (mgx_attn_bwd with this kernel's O / LSE) or, opt-in, e4m3 (attention_fp8_bwd.hip).
 //
 // Three passes:
 //   mgx_attn_fp8_quantize : amax[3][B*H] of Q, K, V; Q8, K8 [B,H,S,128] e4m3; V8t [B,H,128,Sp] e4m3 with the keys of
@@ -15,6 +15,7 @@
 //                           through two LDS buffers, S^T = K Q^T with the accumulator reused as the B operand of
 //                           O^T += Vt P^T, deferred rescale.  A 64-key tile is 4 + 4 MFMAs per wave instead of 16 + 16.
 #include "../../include/mixgrpo_hip.h"
+#include "attn_fp8_quant.h"
 #include "common.h"
 
 #include <type_traits>
@@ -28,24 +29,25 @@ constexpr int K8_TILE = KB * HD;   // 8 KiB
 constexpr int V8_TILE = HD * KB;   // 8 KiB
 constexpr float F8_MAX = 448.0f;
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
 // ------------------------------------------------------------------------------------------------ quantisation
-// amax over the valid region of one tensor of one (b, h): Q / K = S rows of 128, Vt = 128 rows of S (ld Sp).
-__global__ void __launch_bounds__(256) fp8_amax_kernel(const bf16_raw* __restrict__ Q, const bf16_raw* __restrict__ K,
-                                                       const bf16_raw* __restrict__ Vt, uint32_t* __restrict__ amax,
-                                                       int BH, int S, int Sp) {
-  const int bh = blockIdx.x, t = blockIdx.y;
-  const bf16_raw* p;
-  int rows, cols, ld;
-  if (t < 2) { p = (t == 0 ? Q : K) + (long)bh * S * HD; rows = S; cols = HD; ld = HD; }
-  else { p = Vt + (long)bh * HD * Sp; rows = HD; cols = S; ld = Sp; }
+// The passes serve the forward (Q, K, Vt) and the backward (attention_fp8_bwd.hip: Q, K, V, dO and the transposed images of
+// Q, K, dO): attn_fp8_quant.h describes the tensors.
+using mgx_f8::Src;
+using mgx_f8::Srcs;
+using mgx_f8::TSrcs;
+
+// amax over the valid region of tensor blockIdx.y of one (b, h): Q / K = S rows of 128, Vt = 128 rows of S (ld Sp).
+__global__ void __launch_bounds__(256) fp8_amax_kernel(Srcs srcs, uint32_t* __restrict__ amax, int H) {
+  const int bh = blockIdx.x, t = blockIdx.y, BH = gridDim.x;
+  const Src& s = srcs.s[t];
+  const bf16_raw* p = s.p + (long)(bh / H) * s.bstride + (long)(bh % H) * s.hstride;
+  const int cols = s.cols;
   const int cpr = (cols + 7) >> 3;
-  const long nvec = (long)rows * cpr;
+  const long nvec = (long)s.rows * cpr;
   uint32_t m = 0;
   for (long v = (long)blockIdx.z * blockDim.x + threadIdx.x; v < nvec; v += (long)gridDim.z * blockDim.x) {
     const int row = (int)(v / cpr), c8 = (int)(v - (long)row * cpr);
-    const uint4 u = *reinterpret_cast<const uint4*>(p + (long)row * ld + c8 * 8);
+    const uint4 u = *reinterpret_cast<const uint4*>(p + (long)row * s.ld + c8 * 8);
     const uint32_t w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -74,45 +76,73 @@ __device__ __forceinline__ uint32_t quant4(uint32_t w0, uint32_t w1, float sc) {
   return (uint32_t)r;
 }
 
-// Q, K: same row-major layout, 16 elements per thread
-__global__ void __launch_bounds__(256) fp8_quant_rows_kernel(const bf16_raw* __restrict__ Q, const bf16_raw* __restrict__ K,
-                                                             uint8_t* __restrict__ Q8, uint8_t* __restrict__ K8,
-                                                             const float* __restrict__ amax, int BH, long per_bh) {
-  const int t = blockIdx.y;
-  const bf16_raw* src = t == 0 ? Q : K;
-  uint8_t* dst = t == 0 ? Q8 : K8;
-  const long nvec = (long)BH * per_bh / 16;
+// Row-major tensors (rows of 128) -> contiguous [B*H, rows, 128] e4m3, 16 elements per thread; tensor i0 + blockIdx.y
+__global__ void __launch_bounds__(256) fp8_quant_rows_kernel(Srcs srcs, int i0, const float* __restrict__ amax, int BH, int H) {
+  const int t = i0 + blockIdx.y;
+  const Src& s = srcs.s[t];
+  const long per_bh = (long)s.rows * 8;          // 16-element vectors per (b, h)
+  const long nvec = (long)BH * per_bh;
   for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (long)gridDim.x * blockDim.x) {
-    const long e = v * 16;
-    const float sc = f8_scale(amax[t * BH + (int)(e / per_bh)]);
-    const uint4 a = *reinterpret_cast<const uint4*>(src + e), b = *reinterpret_cast<const uint4*>(src + e + 8);
+    const int bh = (int)(v / per_bh);
+    const long rem = v - (long)bh * per_bh;
+    const float sc = f8_scale(amax[t * BH + bh]);
+    const bf16_raw* src = s.p + (long)(bh / H) * s.bstride + (long)(bh % H) * s.hstride + (rem >> 3) * s.ld + (rem & 7) * 16;
+    const uint4 a = *reinterpret_cast<const uint4*>(src), b = *reinterpret_cast<const uint4*>(src + 8);
     uint4 o;
     o.x = quant4(a.x, a.y, sc); o.y = quant4(a.z, a.w, sc); o.z = quant4(b.x, b.y, sc); o.w = quant4(b.z, b.w, sc);
-    *reinterpret_cast<uint4*>(dst + e) = o;
+    *reinterpret_cast<uint4*>(s.dst + v * 16) = o;
   }
 }
 
 // Vt -> V8t.  Position p = 32*h + 16*kb + i of a 64-key block holds key 32*kb + 8*(i >> 2) + 4*h + (i & 3): lane half h
 // of the P V MFMA reads positions 32h .. 32h+31, and element 16*kb + i of its P^T fragment is accumulator register i of
 // S^T block kb, whose row is exactly that key.  One thread = 16 output bytes (one kb, one h): four groups of 4 keys.
-__global__ void __launch_bounds__(256) fp8_quant_vt_kernel(const bf16_raw* __restrict__ Vt, uint8_t* __restrict__ V8t,
-                                                           const float* __restrict__ amax, int BH, int Sp) {
+// The same for every transposed operand of the backward (tensor blockIdx.y); columns >= valid leave as zero bytes.
+__global__ void __launch_bounds__(256) fp8_quant_vt_kernel(TSrcs srcs, const float* __restrict__ amax, int BH, int valid, int Sp) {
+  const bf16_raw* __restrict__ Vt = srcs.s[blockIdx.y].p;
+  uint8_t* __restrict__ V8t = srcs.s[blockIdx.y].dst;
+  const float* am = amax + (long)srcs.s[blockIdx.y].amax_row * BH;
   const int q16 = Sp >> 4;                       // 16-byte output chunks per row
   const long nvec = (long)BH * HD * q16;
   for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (long)gridDim.x * blockDim.x) {
     const long row = v / q16;                    // (bh, d)
     const int c = (int)(v - row * q16), blk = c >> 2, qr = c & 3, h = qr >> 1, kb = qr & 1;
-    const float sc = f8_scale(amax[2 * BH + (int)(row / HD)]);
-    const bf16_raw* src = Vt + row * Sp + blk * 64 + kb * 32 + 4 * h;
+    const float sc = f8_scale(am[(int)(row / HD)]);
+    const int col0 = blk * 64 + kb * 32 + 4 * h;
+    const bf16_raw* src = Vt + row * Sp + col0;
     uint32_t o[4];
 #pragma unroll
     for (int gi = 0; gi < 4; ++gi) {
       const uint2 u = *reinterpret_cast<const uint2*>(src + 8 * gi);
-      o[gi] = quant4(u.x, u.y, sc);
+      const int left = valid - (col0 + 8 * gi);  // valid columns of this group of 4
+      o[gi] = quant4(u.x, u.y, sc) & (left >= 4 ? 0xFFFFFFFFu : left <= 0 ? 0u : (1u << (8 * left)) - 1u);
     }
     *reinterpret_cast<uint4*>(V8t + row * Sp + c * 16) = make_uint4(o[0], o[1], o[2], o[3]);
   }
 }
+
+}  // namespace
+
+void mgx_f8::amax_launch(const Srcs& srcs, int n, float* amax, int B, int H, hipStream_t st) {
+  const int BH = B * H;
+  (void)hipMemsetAsync(amax, 0, sizeof(float) * n * BH, st);   // a failure surfaces in the caller's MGX_CHECK_LAUNCH
+  long elems = 0;
+  for (int i = 0; i < n; ++i) elems = max(elems, (long)srcs.s[i].rows * srcs.s[i].cols);
+  const int zc = max(1, min(64, cdiv(elems / 8, 256 * 8)));
+  fp8_amax_kernel<<<dim3(BH, n, zc), 256, 0, st>>>(srcs, reinterpret_cast<uint32_t*>(amax), H);
+}
+
+void mgx_f8::quant_rows_launch(const Srcs& srcs, int i0, int n, const float* amax, int B, int H, hipStream_t st) {
+  const int BH = B * H;
+  const long nvec = (long)BH * srcs.s[i0].rows * 8;
+  fp8_quant_rows_kernel<<<dim3(min(cdiv(nvec, 256), 16384), n - i0), 256, 0, st>>>(srcs, i0, amax, BH, H);
+}
+
+void mgx_f8::quant_t_launch(const TSrcs& srcs, int n, const float* amax, int BH, int valid, int Sp, hipStream_t st) {
+  fp8_quant_vt_kernel<<<dim3(min(cdiv((long)BH * HD * (Sp / 16), 256), 16384), n), 256, 0, st>>>(srcs, amax, BH, valid, Sp);
+}
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------ attention
 struct AttnF8Args {
@@ -126,20 +156,6 @@ struct AttnF8Args {
   long ldo, o_bstride;
   float scale_log2e;
 };
-
-// K8 tile image: [64 keys][8 chunks of 16 B], chunk ^= (key >> 1) & 7; V8t tile image: [128 d][4 chunks of 16 B],
-// chunk ^= ((d >> 2) ^ (d >> 1)) & 3.  Both checked against the ds_read_b128 lane groups ({0-3,12-15,20-27},
-// {4-11,16-19,28-31} per half): the 16 lanes of a group read the same chunk index of 16 different rows and land on 16
-// different bank quads.
-__device__ __forceinline__ int k8_off(int key, int chunk) { return key * 128 + ((chunk ^ ((key >> 1) & 7)) << 4); }
-__device__ __forceinline__ int v8_off(int d, int chunk) { return d * 64 + ((chunk ^ (((d >> 2) ^ (d >> 1)) & 3)) << 4); }
-
-__device__ __forceinline__ i32x8 frag32(const char* p0, const char* p1) {
-  const uint4 a = *reinterpret_cast<const uint4*>(p0), b = *reinterpret_cast<const uint4*>(p1);
-  i32x8 f;
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-  return f;
-}
 
 #define MFMA_F8(A_, B_, C_) \
   __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A_, B_, C_, 0, 0, 0, one_e8m0, 0, one_e8m0)
@@ -326,17 +342,15 @@ extern "C" int mgx_attn_fp8_quantize(const uint16_t* Q, const uint16_t* K, const
   MGX_REQUIRE(B > 0 && H > 0 && S > 0, "empty attention");
   MGX_REQUIRE(Sp >= S && Sp % 64 == 0, "Sp must be S rounded up to a multiple of 64");
   hipStream_t st = (hipStream_t)stream;
-  const int BH = B * H;
-  if (hipMemsetAsync(amax, 0, sizeof(float) * 3 * BH, st) != hipSuccess) {
-    mgx_set_error("mgx_attn_fp8_quantize: hipMemsetAsync failed");
-    return MGX_ERR_LAUNCH;
-  }
-  const int zc = max(1, min(64, cdiv((long)S * HD / 8, 256 * 8)));
-  fp8_amax_kernel<<<dim3(BH, 3, zc), 256, 0, st>>>(Q, K, Vt, reinterpret_cast<uint32_t*>(amax), BH, S, Sp);
-  const long per_bh = (long)S * HD;
-  fp8_quant_rows_kernel<<<dim3(min(cdiv((long)BH * per_bh / 16, 256), 16384), 2), 256, 0, st>>>(Q, K, Q8, K8, amax, BH,
-                                                                                                  per_bh);
-  fp8_quant_vt_kernel<<<min(cdiv((long)BH * HD * (Sp / 16), 256), 16384), 256, 0, st>>>(Vt, V8t, amax, BH, Sp);
+  mgx_f8::Srcs srcs = {};
+  srcs.s[0] = mgx_f8::rows_src(Q, H, S, Q8);
+  srcs.s[1] = mgx_f8::rows_src(K, H, S, K8);
+  srcs.s[2] = {Vt, (long)H * HD * Sp, (long)HD * Sp, Sp, HD, S, nullptr};
+  mgx_f8::amax_launch(srcs, 3, amax, B, H, st);
+  mgx_f8::quant_rows_launch(srcs, 0, 2, amax, B, H, st);
+  mgx_f8::TSrcs ts = {};
+  ts.s[0] = {Vt, V8t, 2};
+  mgx_f8::quant_t_launch(ts, 1, amax, B * H, Sp, Sp, st);
   MGX_CHECK_LAUNCH();
   return MGX_OK;
 }

@@ -221,7 +221,18 @@ class _Work:
         self.lse = e(B, H, S, dtype=F32)
         self.train = None                         # flux_backward._Train, at its own batch capacity
         self._f8 = None                           # (Q8, K8, V8t, amax): allocated when attention_dtype == "fp8"
+        self._f8_bwd = None                       # (workspace, amax) of the e4m3 attention backward (ops.ATTN_FP8_BWD)
         self._dims = (H, hd)
+
+    def fp8_bwd_workspace(self):
+        """Byte workspace and [4][B*H] amax table of `ops.attn_bwd_fp8`, once, at batch capacity (a smaller batch lays its
+        sections out inside the same bytes)."""
+        if self._f8_bwd is None:
+            H, _ = self._dims
+            dev = self.X.device
+            self._f8_bwd = (torch.empty(ops.attn_bwd_fp8_workspace(self.B, H, self.S, self.Sp), dtype=torch.uint8, device=dev),
+                            torch.empty(4 * self.B * H, dtype=F32, device=dev))
+        return self._f8_bwd
 
     def fp8_operands(self):
         """e4m3 copies of Q, K and the key-permuted V^T plus the per-(batch, head) amax table, at batch capacity."""
@@ -252,6 +263,9 @@ class _WorkView:
     def fp8_operands(self):
         q8, k8, v8t, amax = self.base.fp8_operands()
         return q8[:self.B], k8[:self.B], v8t[:self.B], amax      # amax is laid out [3][B*H] for the CURRENT batch
+
+    def fp8_bwd_workspace(self):
+        return self.base.fp8_bwd_workspace()
 
     @property
     def train(self):

@@ -311,9 +311,15 @@ def _dgrad(model, tr, dC: Rows, N, K, wname, out: Rows, rows=None, epi=EPI_BIAS,
     ops.gemm(dC, Wt[row_lo:row_hi], None, out, row_hi - row_lo, N, epi, aux=aux, ldaux=ldaux, gate=gate, gate_ld=0)
 
 
-def _attn_bwd(w, Q, K, V, Qt, Kt, O, dO, lse, tr, B, H, S, Sp, ldo, o_bstride, scale):
+def _attn_bwd(model, w, Q, K, V, Qt, Kt, O, dO, lse, tr, B, H, S, Sp, ldo, o_bstride, scale):
     """The attention backward of one block into tr.dQ / dK / dV.  On a padded workspace (w.kv_len set; every buffer allocated
-    at S % 256 == 0) the masked-tail pair: rows >= kv_len contribute nothing and their dQ / dK / dV rows come back zero."""
+    at S % 256 == 0) the masked-tail pair: rows >= kv_len contribute nothing and their dQ / dK / dV rows come back zero.
+    With e4m3 attention and ops.ATTN_FP8_BWD the e4m3 backward (never padded: `_pad_kv_rows` keeps fp8 on the plain route)."""
+    if ops.ATTN_FP8_BWD and model.attention_dtype == "fp8":
+        ws, amax = w.fp8_bwd_workspace()
+        ops.attn_bwd_fp8(Q, K, V, Qt, Kt, O, dO, lse, tr.delta, tr.dOt, tr.dQ, tr.dK, tr.dV, ws, amax, B, H, S, Sp, ldo, o_bstride,
+                         scale)
+        return
     if w.kv_len is None:
         ops.attn_bwd(Q, K, V, Qt, Kt, O, dO, lse, tr.delta, tr.dOt, tr.dQ, tr.dK, tr.dV, B, H, S, Sp, ldo, o_bstride, scale)
     elif not ops.attn_bwd_kv(Q, K, V, Qt, Kt, O, dO, lse, tr.delta, tr.dOt, tr.dQ, tr.dK, tr.dV, B, H, S, w.kv_len, ldo, o_bstride,
@@ -392,7 +398,7 @@ def _backward(model, w, tr, sv, dout):
         ops.transpose(Rows.of(stW), 5 * d, Wt, d)
         ops.gemm(dyr, Wt[0:d], None, Rows.of(dO.view(M, pl.ldo)), d, d, EPI_BIAS)
         ops.gemm(dyr, Wt[d:5 * d], None, Rows(dbig[0, 3 * d:], M, 7 * d), 4 * d, d, EPI_DGELU, aux=pl.hid_pre, ldaux=4 * d)
-        _attn_bwd(w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO, pl.lse, tr, B, H, S, Sp, pl.ldo, S * pl.ldo, scale)
+        _attn_bwd(model, w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO, pl.lse, tr, B, H, S, Sp, pl.ldo, S * pl.ldo, scale)
         # qk norm / rope backward writes [dq|dk|dv] straight into columns 0..3d of the [M, 7d] staging matrix
         ops.qk_norm_rope_bwd(pl.qkv, model.W32(f"{p}.attn.norm_q.weight"), model.W32(f"{p}.attn.norm_k.weight"), cos, sin,
                              tr.dQ, tr.dK, tr.dV, dbig, store.view(g32, f"{p}.attn.norm_q.weight"),
@@ -442,7 +448,7 @@ def _backward(model, w, tr, sv, dout):
                    f"{p}.attn.{outn}.bias")
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             _dgrad(model, tr, Rows.of(tr.dy[sl[name]]), d, d, f"{p}.attn.{outn}.weight", srows(dO3, name, d))
-        _attn_bwd(w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO3, pl.lse, tr, B, H, S, Sp, d, S * d, scale)
+        _attn_bwd(model, w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO3, pl.lse, tr, B, H, S, Sp, d, S * d, scale)
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             ops.qk_norm_rope_bwd(pl.qkv[sl[name]], model.W32(f"{p}.attn.{nq}.weight"), model.W32(f"{p}.attn.{nk}.weight"), cos,
                                  sin, tr.dQ, tr.dK, tr.dV, dqkv_all[sl[name]], store.view(g32, f"{p}.attn.{nq}.weight"),

@@ -245,6 +245,34 @@ def attn_fwd_fp8(Q8, K8, V8t, amax, O_ptr_tensor, lse, B, H, S, Sp, ldo, o_bstri
                                  ldo, o_bstride, scale, stream()))
 
 
+# The e4m3 attention backward (csrc/attention_fp8_bwd.hip) behind attention_dtype="fp8": the gradient of the quantised function
+# the forward ran, instead of the bf16 backward on the bf16 operands.  Off by default until it has been measured in a train step.
+ATTN_FP8_BWD = os.environ.get("MGX_ATTN_FP8_BWD", "0") != "0"
+
+
+def attn_bwd_fp8_workspace(B, H, S, Sp):
+    """Bytes of the workspace `attn_bwd_fp8` needs (host code: no GPU)."""
+    n = lib().mgx_attn_bwd_fp8_workspace(B, H, S, Sp)
+    if n < 0:
+        raise ValueError(f"attn_bwd_fp8_workspace: bad sizes B {B} H {H} S {S} Sp {Sp}")
+    return n
+
+
+def attn_bwd_fp8_layout(B, H, S, Sp):
+    """name -> (byte offset, shape) of the workspace sections `mgx_attn_bwd_fp8` fills (include/mixgrpo_hip.h)."""
+    rb, tb = (B * H * S * 128 + 255) // 256 * 256, B * H * 128 * Sp
+    out = {n: (i * rb, (B, H, S, 128)) for i, n in enumerate(("Q8", "K8", "V8", "dO8"))}
+    out.update({n: (4 * rb + i * tb, (B, H, 128, Sp)) for i, n in enumerate(("Q8t", "K8t", "dO8t"))})
+    return out
+
+
+def attn_bwd_fp8(Q, K, V, Qt, Kt, O, dO, lse, delta, dOt, dQ, dK, dV, ws, amax, B, H, S, Sp, ldo, o_bstride, scale):
+    """attn_bwd on the e4m3 MFMA, from the O / lse of attn_fwd_fp8; ws: `attn_bwd_fp8_workspace` bytes, amax: fp32 [4 * B * H]."""
+    check(lib().mgx_attn_bwd_fp8(ptr(Q), ptr(K), ptr(V), ptr(Qt), ptr(Kt), O.data_ptr(), dO.data_ptr(), ptr(lse), ptr(delta),
+                                 ptr(dOt), ptr(dQ), ptr(dK), ptr(dV), ptr(ws), ptr(amax), B, H, S, Sp, ldo, o_bstride, scale,
+                                 ws.numel(), stream()))
+
+
 def skinny_linear(x, W, bias, out, N, K):
     """out[b] = bf16(x[b] @ W^T + bias) for <= 16 rows per call (more rows are chunked)."""
     Bn = x.shape[0]
