@@ -434,6 +434,24 @@ int mgx_nhwc_to_image(const uint16_t* x, long ld, uint16_t* img, int Cout, int H
 /* P[r, :n] = bf16(softmax(scale * S[r, :n])), S fp32 (the mid block's single-head attention over H W <= 16384 tokens) */
 int mgx_softmax_rows_f32(const float* S, long lds, uint16_t* P, long ldp, int M, int n, float scale, void* stream);
 
+/* ---- low-rank adapters (csrc/lora.hip).  A target Linear y = x (W0 + s B A)^T + b with A [r, K], B [N, r]; B is held
+ * transposed (Bt [r, N]) so that both adapter halves are "r rows x wide" and each kernel serves both.  r in {16, 32, 64, 128},
+ * Kin % 64 == 0, any M >= 1; everything else is refused.  No atomics: every result is bit-reproducible.
+ *
+ * Out[M, r] = bf16(scale * In[M, Kin] P[r, Kin]^T): bf16 MFMA, fp32 accumulation, ONE rounding.  Row m of In sits at
+ * (m / in_rpb) * in_bstride + (m % in_rpb) * ld_in elements (as in mgx_transpose_bf16); Out and P are plain matrices. */
+int mgx_lora_proj(const uint16_t* in, const uint16_t* P, uint16_t* out, long M, int Kin, int r, long ld_in, long in_rpb,
+                  long in_bstride, float scale, void* stream);
+/* G[r, Kin] = beta * G + Small[M, r]^T Big[M, Kin], fp32 (beta == 0: G is not read).  Small is a plain [M, r] matrix, Big is
+ * addressed like In above.  The rows are split over workgroups whose partial sums go to `workspace` (fp32,
+ * mgx_lora_wgrad_workspace(M, Kin, r) elements; -1 for sizes the kernel refuses) and are added in a fixed order. */
+long mgx_lora_wgrad_workspace(long M, int Kin, int r);
+int mgx_lora_wgrad(const uint16_t* small, const uint16_t* big, float* G, float* workspace, long workspace_elems, long M, int Kin,
+                   int r, long ld_big, long big_rpb, long big_bstride, float beta, void* stream);
+/* W16[n, k] = bf16(W0[n, k] + s * sum_j Bt[j, n] A[j, k]): fp32 masters in, products and sums in fp64 (j ascending), ONE
+ * rounding to bf16 (an fp32 sum misses bf16(exact) by several ulps where W0 and s B A cancel). */
+int mgx_lora_merge(const float* W0, const float* Bt, const float* A, uint16_t* W16, int N, int K, int r, float s, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,10 @@ SIGNATURES = {
     "mgx_sqnorm_f32": (_I, [_P, _L, _P, _P, _F, _P]),
     "mgx_adamw_step": (_I, [_P, _P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _I, _P, _F, _F, _P]),
     "mgx_scale_f32": (_I, [_P, _L, _F, _P]),
+    "mgx_lora_proj": (_I, [_P, _P, _P, _L, _I, _I, _L, _L, _L, _F, _P]),
+    "mgx_lora_wgrad_workspace": (_L, [_L, _I, _I]),
+    "mgx_lora_wgrad": (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _L, _L, _L, _F, _P]),
+    "mgx_lora_merge": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
 }
 
 _lib = None

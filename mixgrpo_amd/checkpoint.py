@@ -28,6 +28,22 @@ def save_checkpoint(transformer, rank, output_dir, step, epoch):
     return save_dir
 
 
+def save_lora_checkpoint(transformer, rank, output_dir, step, epoch):
+    """The adapter checkpoint of the reference (fastvideo/utils/checkpoint.py:257-298): rank 0 writes
+    `{output_dir}/lora-checkpoint-{step}-{epoch}/pytorch_lora_weights.safetensors` (keys `transformer.<module>.lora_A.weight`
+    [r, K] / `.lora_B.weight` [N, r], fp32) and `lora_config.json` (`step`, `lora_params`: `lora_rank`, `lora_alpha`,
+    `target_modules`).  Deviation: the reference pickles the optimizer state into `lora_optimizer.pt`; here the AdamW moments
+    of the adapters go through `save_resume_state` (`optimizer.safetensors` + `trainer_state.json`) like the full fine-tune's,
+    loaded without unpickling.  The base weights are not written: resume from such a directory reads them from
+    `--pretrained_model_name_or_path`."""
+    main_print(f"--> saving LoRA checkpoint at step {step}")
+    save_dir = os.path.join(output_dir, f"lora-checkpoint-{step}-{epoch}")
+    if rank <= 0:
+        transformer.save_lora(save_dir, step=step)
+    main_print(f"--> LoRA checkpoint saved at step {step}")
+    return save_dir
+
+
 def save_resume_state(save_dir, optimizer, lr_scheduler=None, grpo_states=None, global_step=0, rank=0, epoch=0,
                       steps_done=None):
     """Writes `optimizer.safetensors` (m, v: flat fp32 in the parameter store's order) and `trainer_state.json`.

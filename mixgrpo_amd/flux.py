@@ -299,6 +299,89 @@ class FluxTransformer2DModel(torch.nn.Module):
         self.padded_kv_calls = 0
         self.last_train_route = None              # of the last training forward (FluxFunction): "plain" | "padded_kv"
         self.padded_kv_train_calls = 0
+        self.lora = None                          # lora.LoraStore once adapters are attached (add_lora / load_lora)
+
+    # ------------------------------------------------------------------ low-rank adapters (lora.py)
+    @property
+    def trainable_store(self):
+        """The store the optimizer, the gradient clipping and the DP reduction work on: the adapters' when attached, else
+        the model's own."""
+        return self.store if self.lora is None else self.lora
+
+    @property
+    def trainable_param(self):
+        return self.flat_param if self.lora is None else self.lora_param
+
+    def add_lora(self, rank=16, alpha=None, target_modules=None, seed=0):
+        """Attach rank-`rank` adapters (scale alpha / rank; alpha defaults to rank) to the Linears `target_modules` selects
+        (lora.SUPPORTED_TARGETS; default: the eight attention projections) and freeze everything else: the base weights
+        `store.w32` stay as they are, only the adapters receive gradients and optimizer steps, and the base's fp32 gradient
+        buffer is dropped.  A kaiming-uniform, B zero: every output bit is unchanged until the first step."""
+        from .lora import LoraStore
+        if self.lora is not None:
+            raise MgxError("add_lora: adapters are already attached (unload_lora() first)")
+        lo = LoraStore(self.cfg, self.store.device, rank, rank if alpha is None else alpha, target_modules)
+        lo.init_adapters(seed)
+        self._attach_lora(lo)
+        return self
+
+    def _attach_lora(self, lo):
+        self.lora = lo
+        self.lora_param = torch.nn.Parameter(lo.w32, requires_grad=True)
+        self.flat_param.requires_grad_(False)
+        self.flat_param.grad = None
+        self.store.g32 = None
+        self.config.update(lora_rank=lo.rank, lora_alpha=lo.alpha, lora_target_modules=list(lo.target_modules))
+        lo.merge(self.store)
+
+    def merge_lora(self):
+        """Refresh the targets' bf16 compute copy from the frozen base and the current adapters (after every optimizer step)."""
+        self.lora.merge(self.store)
+
+    def unload_lora(self):
+        """Detach the adapters: the targets' compute copy is the base's again (bit for bit) and the base trains as before."""
+        if self.lora is None:
+            return self
+        self.lora.unmerge(self.store)
+        self.lora = None
+        del self.lora_param
+        for k in ("lora_rank", "lora_alpha", "lora_target_modules"):
+            self.config.pop(k, None)
+        self.flat_param.requires_grad_(True)
+        return self
+
+    def lora_state_dict(self):
+        """{`transformer.<module>.lora_A.weight` [r, K], `transformer.<module>.lora_B.weight` [N, r]}: fp32, the adapter
+        naming of peft / diffusers' `save_lora_weights`.  Neither library is available to test against here: the key format
+        is UNPINNED."""
+        if self.lora is None:
+            raise MgxError("lora_state_dict: no adapters attached")
+        return self.lora.state_dict()
+
+    def save_lora(self, save_dir, step=0):
+        """`pytorch_lora_weights.safetensors` + `lora_config.json` (rank, alpha, target modules, step) into `save_dir`."""
+        from safetensors.torch import save_file
+
+        from .lora import WEIGHTS_NAME, write_lora_config
+        os.makedirs(save_dir, exist_ok=True)
+        sd = {k: v.detach().cpu().contiguous() for k, v in self.lora_state_dict().items()}
+        tmp = os.path.join(save_dir, WEIGHTS_NAME + ".tmp")
+        save_file(sd, tmp)
+        os.replace(tmp, os.path.join(save_dir, WEIGHTS_NAME))
+        write_lora_config(save_dir, self.lora.config(step))
+
+    def load_lora(self, load_dir):
+        """Attach the adapters of a directory `save_lora` / `checkpoint.save_lora_checkpoint` wrote (replacing attached ones)
+        and merge them into the compute copy."""
+        from safetensors.torch import load_file
+
+        from .lora import WEIGHTS_NAME, LoraStore, read_lora_config
+        rank, alpha, targets, _ = read_lora_config(load_dir)
+        self.unload_lora()
+        lo = LoraStore(self.cfg, self.store.device, rank, alpha, targets)
+        lo.load_state_dict(load_file(os.path.join(load_dir, WEIGHTS_NAME)))
+        self._attach_lora(lo)
+        return self
 
     # ------------------------------------------------------------------ parameters / checkpoints
     def state_dict(self, *args, **kwargs):
@@ -314,6 +397,8 @@ class FluxTransformer2DModel(torch.nn.Module):
                 if k in self.store.index:
                     self.store.view(self.store.w32, k).copy_(v.to(F32))
         self.store.sync_bf16()
+        if self.lora is not None:
+            self.lora.merge(self.store)
         return missing, unexpected
 
     def init_synthetic(self, seed=0, std=0.02, bias_std=0.0):
@@ -328,7 +413,7 @@ class FluxTransformer2DModel(torch.nn.Module):
 
     def clip_grad_norm_(self, max_norm):
         """Global L2 norm of the fp32 gradients, scaled in place like torch's clip_grad_norm_ (reference :606)."""
-        g = self.store.ensure_grad()
+        g = self.trainable_store.ensure_grad()
         nsq = torch.zeros(1, dtype=F32, device=g.device)
         ops.sqnorm(g, nsq)
         total = nsq.sqrt()
@@ -630,9 +715,9 @@ class FluxTransformer2DModel(torch.nn.Module):
 
     def forward(self, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections, img_ids,
                 joint_attention_kwargs=None, return_dict=False):
-        if torch.is_grad_enabled() and self.training and self.flat_param.requires_grad:
+        if torch.is_grad_enabled() and self.training and self.trainable_param.requires_grad:
             from .flux_backward import FluxFunction
-            out = FluxFunction.apply(self.flat_param, self, hidden_states, encoder_hidden_states, timestep, guidance,
+            out = FluxFunction.apply(self.trainable_param, self, hidden_states, encoder_hidden_states, timestep, guidance,
                                      txt_ids, pooled_projections, img_ids)
             return (out,)
         with torch.no_grad():

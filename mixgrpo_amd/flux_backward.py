@@ -279,7 +279,10 @@ class FluxFunction(torch.autograd.Function):
 def _wgrad(model, tr, A, K, dC: Rows, N, wname, bname, rows=None):
     """g32[W] += dC^T A ; g32[b] += colsum(dC).  `rows`: number of fused weight rows when W spans several tensors.
     `A`: the [M, K] activation as `Rows`, or a list of column blocks `(Rows, width, gelu)` that make it up side by side --
-    `gelu`: that block is gelu_tanh of the given (kept) pre-activation, applied on the way into the transposed operand."""
+    `gelu`: that block is gelu_tanh of the given (kept) pre-activation, applied on the way into the transposed operand.
+    With adapters attached (model.lora): the rank-r gradients of the targets among these rows, nothing for frozen tensors."""
+    if model.lora is not None:
+        return _lora_wgrad(model, A, K, dC, wname, N if rows else None)
     st = model.store
     g = st.ensure_grad()
     parts = A if isinstance(A, list) else [(A, K, False)]
@@ -298,6 +301,31 @@ def _wgrad(model, tr, A, K, dC: Rows, N, wname, bname, rows=None):
     assert k0 == K
     gw = st.fused(g, wname, N) if rows else st.view(g, wname)
     ops.gemm(Rows.of(dCt), At, None, Rows(gw, N, K), K, Mp, EPI_F32_ACC, beta=1.0, ldw=Mp)
+
+
+def _lora_wgrad(model, X, K, dC: Rows, wname, rows_total):
+    """The low-rank branch of `_wgrad`: for every adapter target among the weight rows of this call (the members of a fused
+    projection are column slices of dC), with s = alpha / r:
+        T = bf16(s X A^T) [M, r];  dT = bf16(s dC B) [M, r];  g[Bt] += T^T dC;  g[A] += dT^T X      (fp32 accumulation)
+    The full dW is never formed; bias gradients are not computed (frozen)."""
+    lo = model.lora
+    members = lo.members(wname, rows_total)
+    if not members:
+        return
+    assert isinstance(X, Rows), "adapter targets take their input as one row-batched matrix"
+    g = lo.ensure_grad()
+    r, M = lo.rank, dC.M
+    dev = lo.device
+    T = ops.scratch("lora_T", M * r, BF16, dev)
+    dT = ops.scratch("lora_dT", M * r, BF16, dev)
+    flat = dC.t.reshape(-1)
+    for module, col, n in members:
+        A16, Bt16 = lo.view(lo.w16, f"{module}.lora_A"), lo.view(lo.w16, f"{module}.lora_Bt")
+        dCm = Rows(flat[col:], M, dC.ld, dC.rpb, dC.bstride)
+        ops.lora_proj(X, A16, T, K, r, lo.scale)
+        ops.lora_proj(dCm, Bt16, dT, n, r, lo.scale)
+        ops.lora_wgrad(T, dCm, lo.view(g, f"{module}.lora_Bt"), n, r, beta=1.0)
+        ops.lora_wgrad(dT, X, lo.view(g, f"{module}.lora_A"), K, r, beta=1.0)
 
 
 def _dgrad(model, tr, dC: Rows, N, K, wname, out: Rows, rows=None, epi=EPI_BIAS, aux=None, ldaux=None, row_lo=0,
@@ -329,10 +357,12 @@ def _attn_bwd(model, w, Q, K, V, Qt, Kt, O, dO, lse, tr, B, H, S, Sp, ldo, o_bst
 
 
 def _skinny_bwd(model, tr, dmod, x, wname, bname, N, K, dx_acc):
-    """Modulation / embedder linear backward: g32[W] += dmod^T x, g32[b] += sum_b dmod, dx_acc += dmod @ W."""
+    """Modulation / embedder linear backward: g32[W] += dmod^T x, g32[b] += sum_b dmod, dx_acc += dmod @ W.  With adapters
+    attached these weights are frozen: only the input-gradient half runs."""
     st = model.store
-    g = st.ensure_grad()
-    ops.skinny_wgrad(dmod, x, st.view(g, wname), st.view(g, bname), N, K)
+    if model.lora is None:
+        g = st.ensure_grad()
+        ops.skinny_wgrad(dmod, x, st.view(g, wname), st.view(g, bname), N, K)
     if dx_acc is not None:
         ops.skinny_dgrad(dmod, st.view(st.w16, wname), dx_acc, N, K)      # straight from the row-major weight
 
@@ -346,7 +376,13 @@ def _backward(model, w, tr, sv, dout):
     st_, cos, sin = sv["st"], sv["cos"], sv["sin"]
     scale, q_scale = model.attn_scale(), model.q_scale()   # (ln 2, scale * log2 e) for the prescaled Q of mgx_attn_fwd_log2
     store = model.store
-    g32 = store.ensure_grad()
+    if model.lora is None:
+        g32 = store.ensure_grad()
+        gnorm = lambda name: store.view(g32, name)
+    else:
+        # the RMSNorm weights are frozen; mgx_qk_norm_rope_bwd_qs still accumulates their gradients somewhere: a sink
+        sink = torch.zeros(cfg.attention_head_dim, dtype=F32, device=dev)
+        gnorm = lambda name: sink
     dst = torch.zeros(B, d, dtype=BF16, device=dev)        # grad wrt st = silu(temb), summed over all users
 
     def srows(t, which, width):
@@ -401,8 +437,8 @@ def _backward(model, w, tr, sv, dout):
         _attn_bwd(model, w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO, pl.lse, tr, B, H, S, Sp, pl.ldo, S * pl.ldo, scale)
         # qk norm / rope backward writes [dq|dk|dv] straight into columns 0..3d of the [M, 7d] staging matrix
         ops.qk_norm_rope_bwd(pl.qkv, model.W32(f"{p}.attn.norm_q.weight"), model.W32(f"{p}.attn.norm_k.weight"), cos, sin,
-                             tr.dQ, tr.dK, tr.dV, dbig, store.view(g32, f"{p}.attn.norm_q.weight"),
-                             store.view(g32, f"{p}.attn.norm_k.weight"), B, H, S, Sp, S, 0, ld_dqkv=7 * d, q_scale=q_scale)
+                             tr.dQ, tr.dK, tr.dV, dbig, gnorm(f"{p}.attn.norm_q.weight"),
+                             gnorm(f"{p}.attn.norm_k.weight"), B, H, S, Sp, S, 0, ld_dqkv=7 * d, q_scale=q_scale)
         dbr = Rows.of(dbig)
         _wgrad(model, tr, Rows.of(pl.nrm1), d, dbr, 7 * d, f"{p}.attn.to_q.weight", f"{p}.attn.to_q.bias", rows=True)
         _dgrad(model, tr, dbr, 7 * d, d, f"{p}.attn.to_q.weight", Rows.of(tr.dnrm), rows=True)
@@ -451,8 +487,8 @@ def _backward(model, w, tr, sv, dout):
         _attn_bwd(model, w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO3, pl.lse, tr, B, H, S, Sp, d, S * d, scale)
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
             ops.qk_norm_rope_bwd(pl.qkv[sl[name]], model.W32(f"{p}.attn.{nq}.weight"), model.W32(f"{p}.attn.{nk}.weight"), cos,
-                                 sin, tr.dQ, tr.dK, tr.dV, dqkv_all[sl[name]], store.view(g32, f"{p}.attn.{nq}.weight"),
-                                 store.view(g32, f"{p}.attn.{nk}.weight"), B, H, S, Sp, rows, s0, q_scale=q_scale)
+                                 sin, tr.dQ, tr.dK, tr.dV, dqkv_all[sl[name]], gnorm(f"{p}.attn.{nq}.weight"),
+                                 gnorm(f"{p}.attn.{nk}.weight"), B, H, S, Sp, rows, s0, q_scale=q_scale)
             _wgrad(model, tr, Rows.of(pl.nrm1[sl[name]]), d, Rows.of(dqkv_all[sl[name]]), 3 * d, f"{p}.attn.{qkvn[0]}.weight",
                    f"{p}.attn.{qkvn[0]}.bias", rows=True)
         for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
@@ -483,5 +519,8 @@ def _backward(model, w, tr, sv, dout):
         ops.ew(h1, da1, dh1, 1)
         _skinny_bwd(model, tr, dh1, x, f"time_text_embed.{name}.linear_1.weight",
                     f"time_text_embed.{name}.linear_1.bias", d, K, None)
-    if model.flat_param.grad is None:
+    if model.lora is not None:
+        if model.lora_param.grad is None:
+            model.lora_param.grad = model.lora.ensure_grad()
+    elif model.flat_param.grad is None:
         model.flat_param.grad = g32

@@ -357,6 +357,36 @@ def attn_bwd_kv_path(B, H, Sa, kv_len, ldo, o_bstride):
     return lib().mgx_attn_bwd_kv_path(B, H, Sa, kv_len, ldo, o_bstride)
 
 
+# ------------------------------------------------------------------------------------------------ low-rank adapters (csrc/lora.hip)
+LORA_RANKS = (16, 32, 64, 128)
+
+
+def lora_proj(inp: Rows, P, out, Kin, r, scale):
+    """out[M, r] = bf16(scale * inp[M, Kin] @ P[r, Kin]^T); `inp` any row-batched view, `P` / `out` plain bf16 matrices."""
+    check(lib().mgx_lora_proj(ptr(inp.t), ptr(P), ptr(out), inp.M, Kin, r, inp.ld, min(inp.rpb, 1 << 40), inp.bstride, float(scale),
+                              stream()))
+
+
+def lora_wgrad_workspace(M, Kin, r):
+    """fp32 elements of the workspace `lora_wgrad` needs (host code: no GPU)."""
+    n = lib().mgx_lora_wgrad_workspace(M, Kin, r)
+    if n < 0:
+        raise ValueError(f"lora_wgrad_workspace: unsupported sizes M {M} Kin {Kin} r {r} (r in {LORA_RANKS}, Kin % 64 == 0, M >= 1)")
+    return n
+
+
+def lora_wgrad(small, big: Rows, G, Kin, r, beta=1.0):
+    """G[r, Kin] (fp32) = beta * G + small[M, r]^T @ big[M, Kin]; `small` plain bf16, `big` any row-batched view."""
+    ws = scratch("lora_wgrad", lora_wgrad_workspace(big.M, Kin, r), F32, G.device)
+    check(lib().mgx_lora_wgrad(ptr(small), ptr(big.t), ptr(G), ptr(ws), ws.numel(), big.M, Kin, r, big.ld, min(big.rpb, 1 << 40),
+                               big.bstride, float(beta), stream()))
+
+
+def lora_merge(W0, Bt, A, W16, N, K, r, s):
+    """W16[N, K] = bf16(W0 + s * Bt[r, N]^T @ A[r, K]) from the fp32 masters: fp64 sum, one rounding."""
+    check(lib().mgx_lora_merge(ptr(W0), ptr(Bt), ptr(A), ptr(W16), N, K, r, float(s), stream()))
+
+
 # ------------------------------------------------------------------------------------------------ VAE decode (csrc/vae.hip)
 def conv3x3(xpad, Wt, bias, out, H, W, C, Cout, ones=None, ld_out=None):
     """out[H W, Cout] (+)= conv3x3(xpad) + bias: xpad zero-bordered NHWC [(H+2), (W+2), C], Wt [Cout, 3, 3, C].

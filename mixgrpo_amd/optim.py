@@ -13,9 +13,11 @@ from . import ops
 
 
 class FusedAdamW:
-    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), weight_decay=1e-4, eps=1e-8):
+    def __init__(self, model, lr=1e-5, betas=(0.9, 0.999), weight_decay=1e-4, eps=1e-8, store=None):
+        """`store`: the flat store to step over (w32 / w16 / g32 / numel); default: the model's trainable one -- its adapter
+        store when adapters are attached (flux.FluxTransformer2DModel.add_lora), else its parameter store."""
         self.model = model
-        self.store = model.store
+        self.store = store if store is not None else getattr(model, "trainable_store", model.store)
         self.lr = float(lr)
         self.base_lr = float(lr)
         self.betas = betas

@@ -51,11 +51,18 @@ class DualFluxSampler:
         self.vae = vae            # mixgrpo_amd.vae.AutoencoderKL (or any object with .config / .decode): needed for image outputs
 
     def load_new_model(self, model_path):
-        """Reference :27-33: a second transformer with the tuned weights (a safetensors file in diffusers key names)."""
+        """Reference :27-33: a second transformer with the tuned weights (a safetensors file in diffusers key names), or -- an
+        adapter directory (`lora_config.json` + `pytorch_lora_weights.safetensors`, checkpoint.save_lora_checkpoint) -- the base
+        transformer's weights with those adapters merged into the compute copy."""
         from safetensors.torch import load_file
 
         from .flux import FluxTransformer2DModel
+        from .lora import is_lora_dir
         self.transformer_new = FluxTransformer2DModel(self.transformer.cfg, device=self.transformer.store.device)
+        if is_lora_dir(model_path):
+            self.transformer_new.load_state_dict(self.transformer.state_dict(), strict=True)
+            self.transformer_new.load_lora(model_path)
+            return
         self.transformer_new.load_state_dict(load_file(model_path), strict=True)
 
     @torch.no_grad()

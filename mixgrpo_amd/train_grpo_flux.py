@@ -179,10 +179,15 @@ def compute_advantages(args, rewards, reward_weights, gathered):
     return adv
 
 
+def _trainable_store(transformer):
+    """The flat store gradients live in: the adapters' when LoRA adapters are attached, else the model's parameter store."""
+    return getattr(transformer, "trainable_store", None) or getattr(transformer, "store", None)
+
+
 def _grad_reducer(transformer):
     """The bucketed SUM all-reduce over the model's flat gradient buffer (dist_utils.GradReducer; mode / overlap from
     `transformer.dp_grad_dtype` / `transformer.dp_overlap`, else the MGX_DP_GRAD_DTYPE / MGX_DP_OVERLAP environment)."""
-    g = transformer.store.ensure_grad()
+    g = _trainable_store(transformer).ensure_grad()
     r = getattr(transformer, "_mgx_grad_reducer", None)
     if r is None or r.flat.data_ptr() != g.data_ptr():
         r = GradReducer(g, mode=getattr(transformer, "dp_grad_dtype", None), overlap=getattr(transformer, "dp_overlap", None))
@@ -194,11 +199,17 @@ def _fused_step(transformer, optimizer, max_grad_norm):
     """clip_grad_norm_ + optimizer.step() (reference :606-607).  With the flat store and FusedAdamW: DP gradient
     all-reduce (sum) -> one sum-of-squares pass -> AdamW with the clip factor inside.  Returns the device grad norm."""
     ws = world_size()
-    store = getattr(transformer, "store", None)
+    store = _trainable_store(transformer)
     if store is not None and hasattr(optimizer, "grad_sqnorm"):
+        if getattr(optimizer, "store", store) is not store:
+            from ._lib import MgxError
+            raise MgxError("the optimizer was built over another store than the model trains (build FusedAdamW after "
+                           "add_lora / load_lora / unload_lora)")
         _grad_reducer(transformer).finish()          # (buckets launched during the backward, if any, + the rest)
         nsq = optimizer.grad_sqnorm()
         optimizer.step(max_grad_norm=max_grad_norm, grad_scale=1.0 / ws, gnorm_sq=nsq)   # (the one pass over the gradients: 8 ms)
+        if getattr(transformer, "lora", None) is not None:
+            transformer.merge_lora()                 # the targets' compute copy follows the stepped adapters
         return nsq.sqrt().squeeze(0) / ws
     if ws > 1:                                        # foreign model: average the per-parameter grads over ranks
         for prm in transformer.parameters():
@@ -303,7 +314,7 @@ def train_one_step(args, device, transformer, vae, reward_function, optimizer, l
                 if last_mb and is_dist() and world_size() > 1 and getattr(transformer, "store", None) is not None:
                     red = _grad_reducer(transformer)
                     if red.overlap:
-                        ranges = transformer.store.block_ranges()
+                        ranges = _trainable_store(transformer).block_ranges()
                         transformer._grad_ready = lambda prefix, r_=red, rg_=ranges: r_.reduce_range(*rg_[prefix], async_op=True)
                         hooked = True
                 try:
@@ -462,6 +473,9 @@ _SWITCHES = ("precondition_outputs", "gradient_checkpointing", "allow_tf32", "us
 # engine options the reference has no flag for (all optional)
 _ENGINE_FLAGS = (("rollout_batch", int, 0), ("train_microbatch", int, 0), ("attention_dtype", str, "bf16"),
                  ("mgx_max_epochs", int, None),
+                 # low-rank adapter fine-tuning (lora.py): frozen base, rank-r adapters on the target modules (comma list of
+                 # diffusers module names; default: the eight attention projections), adapter checkpoints
+                 ("lora_rank", int, 16), ("lora_alpha", float, None), ("lora_target_modules", str, None),
                  # "package.module:factory" -- factory(args) -> {RewardClassName: callable(images, prompts) -> scores}: the
                  # reward models of the decode + reward stage (their weights are not part of this engine; the reference builds
                  # its own from HF-hub names at fastvideo/train_grpo_flux.py:639-651)
@@ -483,6 +497,7 @@ def build_parser():
     for name, typ, default in _ENGINE_FLAGS:
         p.add_argument("--" + name, type=typ, default=default)
     p.add_argument("--skip_dead_backward", action="store_true", default=False)
+    p.add_argument("--use_lora", action="store_true", default=False)
     return p
 
 
@@ -545,8 +560,9 @@ def main(args, reward_function=None, reward_weights=None, reward_models=None):
     from torch.utils.data import DataLoader
     from torch.utils.data.distributed import DistributedSampler
 
-    from .checkpoint import (load_resume_position, load_resume_state, load_rng_state, save_checkpoint, save_resume_state,
-                             save_rng_state)
+    from .checkpoint import (load_resume_position, load_resume_state, load_rng_state, save_checkpoint, save_lora_checkpoint,
+                             save_resume_state, save_rng_state)
+    from .lora import is_lora_dir, parse_target_modules
     from .flux import FluxTransformer2DModel
     from .grpo_states import GRPOTrainingStates
     from .latent_flux_rl_datasets import LatentDataset, latent_collate_function
@@ -571,11 +587,25 @@ def main(args, reward_function=None, reward_weights=None, reward_models=None):
             with open(os.path.join(run_dir, "args.json"), "w") as f:
                 json.dump({k: v for k, v in vars(args).items()}, f, indent=4, default=str)
 
-    model_path = args.resume_from_checkpoint or args.pretrained_model_name_or_path
+    # an adapter checkpoint (lora-checkpoint-{step}-{epoch}) holds no base weights: those come from the pretrained model
+    resume_lora = is_lora_dir(args.resume_from_checkpoint)
+    use_lora = bool(getattr(args, "use_lora", False)) or resume_lora
+    if use_lora:
+        parse_target_modules(args.lora_target_modules)           # an unsupported name fails here, before any weight is read
+    model_path = args.pretrained_model_name_or_path if resume_lora else \
+        (args.resume_from_checkpoint or args.pretrained_model_name_or_path)
     main_print(f"--> loading model from {model_path}")
     transformer = FluxTransformer2DModel.from_pretrained(model_path, device=device, subfolder="transformer", torch_dtype=F32)
     transformer.attention_dtype = args.attention_dtype
     transformer.train()
+    if resume_lora:                                              # adapters before the optimizer: its moments are theirs
+        transformer.load_lora(args.resume_from_checkpoint)
+        main_print(f"--> adapters loaded from {args.resume_from_checkpoint}")
+    elif use_lora:
+        transformer.add_lora(args.lora_rank, args.lora_alpha, args.lora_target_modules, seed=args.seed or 0)
+    if use_lora:
+        main_print(f"--> LoRA: rank {transformer.lora.rank} alpha {transformer.lora.alpha} on {len(transformer.lora.targets)} "
+                   f"Linears ({transformer.lora.numel} adapter parameters); the base is frozen")
     optimizer = FusedAdamW(transformer, lr=args.learning_rate, betas=(0.9, 0.999), weight_decay=args.weight_decay, eps=1e-8)
     # the reference's call (:726-734); an unknown name fails here with the list of supported ones
     lr_scheduler = get_scheduler(args.lr_scheduler, optimizer=optimizer, num_warmup_steps=args.lr_warmup_steps,
@@ -650,7 +680,8 @@ def main(args, reward_function=None, reward_weights=None, reward_models=None):
             start_time = time.time()
             if step % args.checkpointing_steps == 0 and run_dir is not None and \
                     not (resumed and step == first_step and epoch == start_epoch):
-                d = save_checkpoint(transformer, rk, run_dir, step, epoch)
+                d = save_lora_checkpoint(transformer, rk, run_dir, step, epoch) if use_lora else \
+                    save_checkpoint(transformer, rk, run_dir, step, epoch)
                 # (what the NEXT step needs to continue: it is `step` itself that has not run yet)
                 save_resume_state(d, optimizer, lr_scheduler, grpo_states, global_step=step - 1, rank=rk, epoch=epoch,
                                   steps_done=global_step)
