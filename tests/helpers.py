@@ -1,4 +1,4 @@
-"""Shared test helpers: fixture loading."""
+"""Shared test helpers: fixture loading, exact-grid operands, process groups."""
 import json
 import os
 
@@ -38,6 +38,23 @@ def assert_same(a, b, exact=True, rtol=2e-6, atol=2e-6):
         fin = torch.isfinite(b)
         assert torch.equal(a[~fin & ~torch.isnan(b)], b[~fin & ~torch.isnan(b)])
         assert torch.allclose(a[fin].float(), b[fin].float(), rtol=rtol, atol=atol), (a[fin].float() - b[fin].float()).abs().max()
+
+
+def grid(shape, lo, hi, div, gen, dtype=None, device="cuda"):
+    """randint(lo, hi) / div: operands of the exact-sum tests.  With small integers over a power of two every partial sum is
+    exact in fp32, so a kernel must give the fp64 result bit for bit in whatever order it adds."""
+    import torch
+    x = torch.randint(lo, hi, shape, generator=gen, device=device).to(torch.float32) / div
+    return x.to(torch.bfloat16 if dtype is None else dtype)
+
+
+def sentinel(shape, device="cuda"):
+    """A bf16 tensor whose bit patterns run 1 .. 251 (denormals): non-zero everywhere and no value of any `grid`, for
+    pre-filling buffers whose untouched or zero-filled parts a test checks."""
+    import math
+
+    import torch
+    return (torch.arange(math.prod(shape), device=device) % 251 + 1).to(torch.int16).view(torch.bfloat16).view(shape)
 
 
 def oracle_flux(cfg, P, device=None):

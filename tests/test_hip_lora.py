@@ -11,15 +11,11 @@ import pytest
 import torch
 
 from oracle import mmdit as OM
-from helpers import run_ranks
+from helpers import grid as _grid, run_ranks
 from test_hip_mmdit import build_pair, make_inputs, small_cfg
 
 pytestmark = pytest.mark.gpu
 BF16, F32 = torch.bfloat16, torch.float32
-
-
-def _grid(shape, lo, hi, div, gen, dtype=BF16):
-    return (torch.randint(lo, hi, shape, generator=gen, device="cuda").to(F32) / div).to(dtype)
 
 
 def _rel(a, b):
@@ -44,7 +40,13 @@ def _operand(M, Kin, layout, gen, make):
 
 
 EXACT_CASES = [(1, 512, 16, "plain"), (63, 512, 64, "plain"), (177, 2048, 128, "plain"), (1100, 512, 16, "plain"),
-               (1100, 2048, 64, "plain"), (1100, 512, 128, "plain"), (177, 512, 64, "cols"), (177, 512, 16, "batched")]
+               (1100, 2048, 64, "plain"), (1100, 512, 128, "plain"), (177, 512, 64, "cols"), (177, 512, 16, "batched"),
+               # Kin = 64: proj has 2 K-steps for its 4 waves, and the only 128-column block of the wgrad is half empty
+               (63, 64, 16, "plain"),
+               # r = 32: lora_proj_kernel<32> / lora_wgrad_kernel<32> (their own small_stride, 48, and staging count);
+               # Kin % 128 = 64: the last column block of the wgrad is half empty (`c0 + ch*8 < Kin`, `col < Kin`)
+               (177, 192, 32, "plain"), (1100, 512, 32, "plain"), (177, 192, 32, "cols"), (177, 64, 32, "batched"),
+               (177, 192, 128, "plain")]
 
 
 @pytest.mark.parametrize("M,Kin,r,layout", EXACT_CASES)
@@ -77,7 +79,7 @@ def test_proj_and_wgrad_exact_on_the_grid_and_deterministic(M, Kin, r, layout):
         assert ops.lora_wgrad_workspace(M, Kin, r) > r * Kin                # several row chunks: the second stage really adds
 
 
-@pytest.mark.parametrize("M,Kin,r", [(177, 512, 16), (1100, 2048, 64), (1100, 512, 128)])
+@pytest.mark.parametrize("M,Kin,r", [(177, 512, 16), (1100, 2048, 64), (1100, 512, 128), (1100, 192, 32)])
 def test_proj_and_wgrad_random_vs_fp64(M, Kin, r):
     from mixgrpo_amd import ops
     from mixgrpo_amd.ops import Rows

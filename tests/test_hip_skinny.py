@@ -5,6 +5,8 @@ bf16 result per linear, bf16 accumulation of the per-user gradients of silu(temb
 import pytest
 import torch
 
+from helpers import grid as _grid, sentinel as _sentinel
+
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
 
@@ -53,3 +55,71 @@ def test_skinny_linear_and_wgrad_vs_autograd():
     ops.skinny_wgrad(dout, x, dW, db, N, K)
     assert torch.allclose(dW, dW0 + (dout.float().t() @ x.float()), rtol=1e-5, atol=1e-5)
     assert torch.allclose(db, db0 + dout.float().sum(0), rtol=1e-5, atol=1e-5)
+
+
+# ---------------------------------------------------------------------------------------------------- exact-grid edges
+# Operands on a grid whose every partial sum is exact in fp32 (x, bias, dout: randint(-4, 5) / 8; W: randint(-2, 3) / 4; products
+# are multiples of 1/32 with |sum| <= 768 / 4), so any split of K over the waves and any order give the fp64 result, and the
+# one bf16 rounding of the output is the reference's.  Outputs are pre-filled with `helpers.sentinel`.
+F32, I16 = torch.float32, torch.int16
+
+
+SKINNY_LINEAR_CASES = [(1, 48, 32, True),        # one K-step: three of the four waves idle
+                       (7, 40, 160, True),       # 5 K-steps split 2 / 2 / 1 / 0; N % 16 = 8: the row clamp and the n < N mask
+                       (16, 16, 544, True),      # 17 steps: 160 per wave = the 128-step loop + the 32-step tail; row 15 stores
+                       (17, 40, 256, True),      # the wrapper's chunks of 16 + 1 rows; K of the timestep embedding
+                       (3, 24, 768, True),       # K of the pooled text projection
+                       (7, 40, 160, False)]      # bias == NULL
+
+
+@pytest.mark.parametrize("Bn,N,K,with_bias", SKINNY_LINEAR_CASES)
+def test_skinny_linear_exact_on_the_grid(Bn, N, K, with_bias):
+    from mixgrpo_amd import ops
+    gen = torch.Generator(device="cuda").manual_seed(Bn * 1000 + N + K)
+    x, W = _grid((Bn, K), -4, 5, 8, gen), _grid((N, K), -2, 3, 4, gen)
+    b = _grid((N,), -4, 5, 8, gen) if with_bias else None
+    want = x.double() @ W.double().t()
+    if with_bias:
+        want = want + b.double()
+    sent = _sentinel((Bn + 2, N))
+    out = sent.clone()                                                  # over-allocated: rows >= Bn must stay as they are
+    ops.skinny_linear(x, W, b, out, N, K)
+    assert torch.equal(out[:Bn], want.to(BF16))
+    assert torch.equal(out[Bn:].view(I16), sent[Bn:].view(I16))
+
+
+def test_skinny_linear_on_column_slices():
+    """x and out as column slices of wider buffers (row strides > K and > N): nothing outside the slice is written."""
+    from mixgrpo_amd import ops
+    Bn, N, K = 7, 40, 160
+    gen = torch.Generator(device="cuda").manual_seed(21)
+    xbig, W, b = _grid((Bn, K + 16), -4, 5, 8, gen), _grid((N, K), -2, 3, 4, gen), _grid((N,), -4, 5, 8, gen)
+    x = xbig[:, 8:8 + K]                                                # 16-byte aligned rows, stride K + 16
+    sent = _sentinel((Bn + 2, N + 11))
+    obig = sent.clone()
+    out = obig[:, 3:3 + N]
+    assert x.stride(0) > K and out.stride(0) > N
+    ops.skinny_linear(x, W, b, out, N, K)
+    assert torch.equal(out[:Bn], (x.double() @ W.double().t() + b.double()).to(BF16))
+    keep = torch.ones_like(sent, dtype=torch.bool)
+    keep[:Bn, 3:3 + N] = False
+    assert torch.equal(obig.view(I16)[keep], sent.view(I16)[keep])
+
+
+SKINNY_WGRAD_CASES = [(1, 3, 4, True),           # one active thread in all
+                      (7, 40, 1028, True),       # two column blocks, the second with one active thread
+                      (16, 5, 2048, True),       # all 16 rows, two full column blocks
+                      (17, 8, 1024, True),       # chunks of 16 + 1 rows: dW and dbias receive both
+                      (7, 40, 1028, False)]      # dbias == NULL
+
+
+@pytest.mark.parametrize("Bn,N,K,with_bias", SKINNY_WGRAD_CASES)
+def test_skinny_wgrad_exact_on_the_grid(Bn, N, K, with_bias):
+    from mixgrpo_amd import ops
+    gen = torch.Generator(device="cuda").manual_seed(Bn * 1000 + N + K)
+    dout, x = _grid((Bn, N), -4, 5, 8, gen), _grid((Bn, K), -4, 5, 8, gen)
+    dW0, db0 = _grid((N, K), -4, 5, 8, gen, dtype=F32), _grid((N,), -4, 5, 8, gen, dtype=F32)
+    dW, db = dW0.clone(), db0.clone()
+    ops.skinny_wgrad(dout, x, dW, db if with_bias else None, N, K)
+    assert torch.equal(dW.double(), dW0.double() + dout.double().t() @ x.double())
+    assert torch.equal(db.double(), db0.double() + (dout.double().sum(0) if with_bias else 0.0))
