@@ -114,10 +114,13 @@ int mgx_unpack_latents(const void* in, void* out, int B, int C, int H, int W, in
 
 /* ------------------------------------------------------------------------------------------------ GRPO
  * Group-relative advantage (train_grpo_flux.py:440-491): per group of G consecutive rewards,
- * (r-mean)/(unbiased std+1e-8), statistics over the upper (1-trimmed_ratio) part when trimmed_ratio>0;
+ * (r-mean)/(unbiased std+1e-8).  trim < 0: statistics over the whole group in its own order (trimmed_ratio <= 0);
+ * trim >= 0: over the sorted group without its `trim` smallest rewards, also for trim == 0.  The caller forms
+ * trim = min(int(G * trimmed_ratio), G - 1) in DOUBLE, as the reference does (:454; a float product differs from it
+ * for 107 of the (G <= 1024, ratio k/100) pairs); trim >= G is refused.
  * out[i] (+)= weight * advantage (accumulate!=0 implements the multi-reward sum of :465-467). */
-int mgx_group_advantage(const float* rewards, float* out, int n, int G, float trimmed_ratio, float weight,
-                        int accumulate, void* stream);
+int mgx_group_advantage(const float* rewards, float* out, int n, int G, int trim, float weight, int accumulate,
+                        void* stream);
 /* Global normalisation for use_group=False (:498): (r - mean(all))/(std(all)+1e-8); all = gathered rewards */
 int mgx_global_advantage(const float* rewards, const float* gathered, float* out, int n, int n_all, void* stream);
 

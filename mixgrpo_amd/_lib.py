@@ -52,7 +52,7 @@ SIGNATURES = {
     "mgx_x0_pred": (_I, [_P, _P, _P, _L, _F, _P]),
     "mgx_pack_latents": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "mgx_unpack_latents": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
-    "mgx_group_advantage": (_I, [_P, _P, _I, _I, _F, _F, _I, _P]),
+    "mgx_group_advantage": (_I, [_P, _P, _I, _I, _I, _F, _I, _P]),
     "mgx_global_advantage": (_I, [_P, _P, _P, _I, _I, _P]),
     "mgx_grpo_loss": (_I, [_P, _P, _P, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
     "mgx_gemm_bf16": (_I, [_P] * 6 + [_L, _I, _I, _I] + [_L] * 8 + [_I, _F, _P]),

@@ -9,8 +9,9 @@ namespace {
 constexpr int kMaxGroup = 1024;
 
 // one block per group; thread 0 does the (<=1024-element) statistics serially in the reference's order
-__global__ void group_adv_kernel(const float* __restrict__ r, float* __restrict__ out, int G, float trimmed_ratio,
-                                 float weight, int accumulate) {
+// trim < 0: untrimmed; else the statistics skip the `trim` smallest rewards (0 <= trim < G, formed on the host in double)
+__global__ void group_adv_kernel(const float* __restrict__ r, float* __restrict__ out, int G, int trim, float weight,
+                                 int accumulate) {
   __shared__ float srt[kMaxGroup];
   __shared__ float mean_s, std_s;
   const float* g = r + (long)blockIdx.x * G;
@@ -28,11 +29,9 @@ __global__ void group_adv_kernel(const float* __restrict__ r, float* __restrict_
   if (threadIdx.x == 0) {
     int lo = 0, cnt = G;
     const float* src = g;  // untrimmed statistics run over the group in its own order
-    if (trimmed_ratio > 0.f) {
-      int t = (int)((float)G * trimmed_ratio);
-      if (t > G - 1) t = G - 1;
-      lo = t;
-      cnt = G - t;
+    if (trim >= 0) {   // sorted order even when nothing is trimmed, as the reference sorts whenever the ratio is > 0
+      lo = trim;
+      cnt = G - trim;
       src = srt;
     }
     float s = 0.f;
@@ -112,14 +111,15 @@ __global__ void grpo_loss_kernel(const float* __restrict__ nlp, const float* __r
 
 }  // namespace
 
-extern "C" int mgx_group_advantage(const float* rewards, float* out, int n, int G, float trimmed_ratio, float weight,
+extern "C" int mgx_group_advantage(const float* rewards, float* out, int n, int G, int trim, float weight,
                                    int accumulate, void* stream) {
   MGX_REQUIRE(rewards && out, "null argument");
   MGX_REQUIRE(G > 0 && G <= kMaxGroup, "group size must be in 1..1024");
+  MGX_REQUIRE(trim < G, "trim count must leave one reward: min(int(G * ratio), G - 1), or negative for untrimmed");
   MGX_REQUIRE(n >= 0, "negative length");
   const int groups = n / G;   // a ragged tail is left untouched, as in the reference's range(n // G)
   if (groups == 0) return MGX_OK;
-  group_adv_kernel<<<groups, 64, 0, (hipStream_t)stream>>>(rewards, out, G, trimmed_ratio, weight, accumulate);
+  group_adv_kernel<<<groups, 64, 0, (hipStream_t)stream>>>(rewards, out, G, trim, weight, accumulate);
   MGX_CHECK_LAUNCH();
   return MGX_OK;
 }

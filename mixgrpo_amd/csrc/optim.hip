@@ -33,7 +33,11 @@ __global__ void sqnorm_finish_kernel(const double* __restrict__ part, int nb, fl
   a = wave_sum_d(a);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
   __syncthreads();
-  if (threadIdx.x == 0) out[0] = beta * out[0] + (float)(red[0] + red[1] + red[2] + red[3]);
+  if (threadIdx.x == 0) {
+    // beta == 0 overwrites: the old value is not read (0 * inf and 0 * NaN would keep a non-finite norm alive for ever)
+    const float s = (float)(red[0] + red[1] + red[2] + red[3]);
+    out[0] = beta == 0.f ? s : beta * out[0] + s;
+  }
 }
 
 // Scalar coefficients exactly as torch.optim.AdamW's (foreach) step forms them: in Python DOUBLE precision on the host, then
@@ -57,7 +61,7 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ w, bf16_
   if (gnorm_sq) {
     const float total = sqrtf(gnorm_sq[0]) * grad_scale;
     const float c = a.max_norm / (total + 1e-6f);
-    clip *= c < 1.0f ? c : 1.0f;
+    clip *= c >= 1.0f ? 1.0f : c;   // torch.clamp(coef, max=1.0): a NaN coefficient stays NaN (clip_grad_norm_)
   }
   for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
     float4 pw = *reinterpret_cast<float4*>(w + i);

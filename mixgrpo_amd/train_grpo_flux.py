@@ -155,20 +155,29 @@ def sample_reference_model(args, device, transformer, vae, encoder_hidden_states
     return rewards, all_latents, all_log_probs, sigma_schedule, all_image_ids
 
 
+def trim_count(G, trimmed_ratio):
+    """`mgx_group_advantage`'s trim argument: the reference's `min(int(len * ratio), len - 1)` (train_grpo_flux.py:454,481)
+    in Python double -- the kernel never sees the ratio -- or -1 (untrimmed) where the reference's `ratio > 0` is false."""
+    if not trimmed_ratio > 0:
+        return -1
+    return min(int(G * trimmed_ratio), G - 1)
+
+
 def compute_advantages(args, rewards, reward_weights, gathered):
     """Group-relative (or global) advantages on the device (reference train_grpo_flux.py:439-501)."""
     G = args.num_generations
+    trim = trim_count(G, args.trimmed_ratio)
     if args.use_group:
         if args.multi_reward_mix == "advantage_aggr":
             first = next(iter(rewards.values()))
             adv = torch.zeros_like(first)
             for k, r in rewards.items():
-                check(lib().mgx_group_advantage(ptr(r.contiguous()), ptr(adv), r.numel(), G, float(args.trimmed_ratio),
+                check(lib().mgx_group_advantage(ptr(r.contiguous()), ptr(adv), r.numel(), G, trim,
                                                 float(reward_weights[k]), 1, stream()))
             return adv
         r = rewards.contiguous()
         adv = torch.zeros_like(r)
-        check(lib().mgx_group_advantage(ptr(r), ptr(adv), r.numel(), G, float(args.trimmed_ratio), 1.0, 0, stream()))
+        check(lib().mgx_group_advantage(ptr(r), ptr(adv), r.numel(), G, trim, 1.0, 0, stream()))
         return adv
     if args.multi_reward_mix == "advantage_aggr":
         raise ValueError("multi_reward_mix 'advantage_aggr' is not supported when use_group is False.")

@@ -45,3 +45,35 @@ def test_schedules_follow_the_reference_formulas(name, warmup, total, num_cycles
 def test_unknown_name_fails_with_the_list():
     with pytest.raises(ValueError, match="constant_with_warmup"):
         get_scheduler("piecewise_constant", _Opt(1e-5))
+
+
+def test_fp32_torch_adamw_stays_inside_the_fp64_budget():
+    """The premise of tests/test_hip_optim.py's elementwise AdamW bounds (derived in tests/optim_refs.py): a plain fp32
+    evaluation -- torch.optim.AdamW (foreach) on the first 2^16 elements of the same data -- stays inside the budget around
+    the fp64 recurrence, over two steps from zero moments and from non-zero moments at large step counts."""
+    import optim_refs as R
+    n = 1 << 16
+    w0, g = R.adamw_data(0, n)
+    worst = [0.0, 0.0, 0.0]
+
+    def compare(got, ref, tol, k):
+        for i, (a, b, t) in enumerate(zip(got, ref, tol)):
+            frac = ((a.double() - b).abs() / t.clamp_min(1e-300)).max().item()
+            assert frac <= 1.0, (k, "wmv"[i], frac)
+            worst[i] = max(worst[i], frac)
+
+    w, m, v = w0, torch.zeros(n), torch.zeros(n)
+    ref, tol = [w0.double(), torch.zeros(n, dtype=R.F64), torch.zeros(n, dtype=R.F64)], R.zeros_like3(w0)
+    for step in (1, 2):
+        w, m, v = R.torch_adamw_step(w, m, v, g, step, **R.HP)
+        R.adamw_ref_step(*ref, tol, g.double(), step=step, **R.HP)
+        compare((w, m, v), ref, tol, step)
+    print("two steps, fp32 torch / budget (w, m, v):", [round(x, 3) for x in worst])
+    worst = [0.0, 0.0, 0.0]
+    m0, v0 = R.hashed(0, n, 3) * 0.01, (R.hashed(0, n, 4) + 0.5) * 1e-4
+    for step in (1000, 100000):
+        got = R.torch_adamw_step(w0, m0, v0, g, step, **R.HP)
+        ref, tol = [w0.double(), m0.double(), v0.double()], R.zeros_like3(w0)
+        R.adamw_ref_step(*ref, tol, g.double(), step=step, **R.HP)
+        compare(got, ref, tol, step)
+    print("late steps, fp32 torch / budget (w, m, v):", [round(x, 3) for x in worst])
