@@ -24,7 +24,8 @@ import torch
 
 from . import ops
 from ._lib import MgxError
-from .ops import BF16, F32, Rows, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES
+from .arch import describe
+from .ops import BF16, F32, Rows, EPI_BIAS_GELU, EPI_BIAS_GATE_RES
 
 
 @dataclass
@@ -52,107 +53,40 @@ class FluxConfig:
 
 
 def param_layout(cfg: FluxConfig) -> List[Tuple[str, Tuple[int, ...]]]:
-    """Flat order of the parameters (diffusers names).  q|k|v weights (and biases) are adjacent on purpose."""
-    d, hd = cfg.dim, cfg.attention_head_dim
-    out = []
-
-    def lin(name, o, i):
-        out.append((name + ".weight", (o, i)))
-        out.append((name + ".bias", (o,)))
-
-    def qkv(prefix, names):
-        for n in names:
-            out.append((f"{prefix}.{n}.weight", (d, d)))
-        for n in names:
-            out.append((f"{prefix}.{n}.bias", (d,)))
-
-    lin("x_embedder", d, cfg.in_channels)
-    lin("context_embedder", d, cfg.joint_attention_dim)
-    embs = ["timestep_embedder"] + (["guidance_embedder"] if cfg.guidance_embeds else []) + ["text_embedder"]
-    for e in embs:
-        lin(f"time_text_embed.{e}.linear_1", d, cfg.pooled_projection_dim if e == "text_embedder" else 256)
-        lin(f"time_text_embed.{e}.linear_2", d, d)
-    for i in range(cfg.num_layers):
-        p = f"transformer_blocks.{i}"
-        lin(f"{p}.norm1.linear", 6 * d, d)
-        lin(f"{p}.norm1_context.linear", 6 * d, d)
-        qkv(f"{p}.attn", ("to_q", "to_k", "to_v"))
-        qkv(f"{p}.attn", ("add_q_proj", "add_k_proj", "add_v_proj"))
-        lin(f"{p}.attn.to_out.0", d, d)
-        lin(f"{p}.attn.to_add_out", d, d)
-        for n in ("norm_q", "norm_k", "norm_added_q", "norm_added_k"):
-            out.append((f"{p}.attn.{n}.weight", (hd,)))
-        for ff in ("ff", "ff_context"):
-            lin(f"{p}.{ff}.net.0.proj", 4 * d, d)
-            lin(f"{p}.{ff}.net.2", d, 4 * d)
-    for i in range(cfg.num_single_layers):
-        p = f"single_transformer_blocks.{i}"
-        lin(f"{p}.norm.linear", 3 * d, d)
-        # to_q | to_k | to_v | proj_mlp adjacent (weights, then biases): one [7d, d] operand for the backward GEMMs
-        for n in ("attn.to_q", "attn.to_k", "attn.to_v"):
-            out.append((f"{p}.{n}.weight", (d, d)))
-        out.append((f"{p}.proj_mlp.weight", (4 * d, d)))
-        for n in ("attn.to_q", "attn.to_k", "attn.to_v"):
-            out.append((f"{p}.{n}.bias", (d,)))
-        out.append((f"{p}.proj_mlp.bias", (4 * d,)))
-        lin(f"{p}.proj_out", d, 5 * d)
-        for n in ("norm_q", "norm_k"):
-            out.append((f"{p}.attn.{n}.weight", (hd,)))
-    lin("norm_out.linear", 2 * d, d)
-    lin("proj_out", cfg.patch_size * cfg.patch_size * cfg.in_channels, d)
-    return out
+    """Flat order of the parameters (diffusers names), as `arch.describe` lays them out."""
+    return [(name, shape) for name, (_, shape) in describe(cfg).index.items()]
 
 
 class ParamStore:
     """Flat fp32 master + bf16 mirror (+ fp32 grad / Adam moments on demand), addressed by diffusers names."""
 
-    ALIGN = 64
-
     def __init__(self, cfg: FluxConfig, device):
         self.cfg = cfg
         self.device = torch.device(device)
-        self.index: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
-        off = 0
-        for name, shape in param_layout(cfg):
-            self.index[name] = (off, shape)
-            n = 1
-            for s in shape:
-                n *= s
-            off += (n + self.ALIGN - 1) // self.ALIGN * self.ALIGN
-        self.numel = off
-        self.w32 = torch.zeros(off, dtype=F32, device=self.device)
-        self.w16 = torch.zeros(off, dtype=BF16, device=self.device)
+        self.arch = describe(cfg)
+        self.index, self.numel = self.arch.index, self.arch.numel       # {name: (element offset, shape)} in flat order
+        self.w32 = torch.zeros(self.numel, dtype=F32, device=self.device)
+        self.w16 = torch.zeros(self.numel, dtype=BF16, device=self.device)
         self.g32 = None
 
     def view(self, buf, name):
         off, shape = self.index[name]
-        n = 1
-        for s in shape:
-            n *= s
-        return buf[off:off + n].view(shape)
+        return buf[off:off + math.prod(shape)].view(shape)
 
-    def fused(self, buf, first, rows_total):
-        """View of `rows_total` rows starting at tensor `first` (adjacent tensors of equal width)."""
-        off, shape = self.index[first]
-        if len(shape) == 1:
-            return buf[off:off + rows_total]
-        return buf[off:off + rows_total * shape[1]].view(rows_total, shape[1])
+    def weight(self, buf, lin):
+        """The [N, K] weight of an `arch.Linear` (a fused one: its members' rows, adjacent in the buffer) in flat buffer `buf`."""
+        return buf[lin.w_off:lin.w_off + lin.N * lin.K].view(lin.N, lin.K)
+
+    def bias(self, buf, lin):
+        return buf[lin.b_off:lin.b_off + lin.N]
 
     def block_ranges(self):
         """{block prefix: (lo, hi)} element ranges of the flat buffers, in layout order (transformer blocks; everything
         before / after them under "head" / "tail").  Contiguous and 64-aligned: the buckets of the DP gradient reduction."""
-        names = list(self.index)
-        key = lambda n: ".".join(n.split(".")[:2]) if n.startswith(("transformer_blocks.", "single_transformer_blocks.")) \
-            else ("head" if self.index[n][0] < self.index["norm_out.linear.weight"][0] else "tail")
-        out, cur, lo = {}, None, 0
-        for n in names:
-            k = key(n)
-            if k != cur:
-                if cur is not None:
-                    out[cur] = (lo, self.index[n][0])
-                cur, lo = k, self.index[n][0]
-        out[cur] = (lo, self.numel)
-        return out
+        a = self.arch       # (a block's first tensor is its AdaLN modulation; the double blocks' image stream's comes first)
+        starts = [("head", 0)] + [(b.prefix, b.streams[1].norm.w_off) for b in a.double] + \
+                 [(b.prefix, b.norm.w_off) for b in a.single] + [("tail", a.norm_out.w_off), (None, self.numel)]
+        return {k: (lo, hi) for (k, lo), (_, hi) in zip(starts, starts[1:])}
 
     def sync_bf16(self):
         self.w16.copy_(self.w32)
@@ -290,6 +224,7 @@ class FluxTransformer2DModel(torch.nn.Module):
         if dev.type != "cuda":
             raise MgxError("FluxTransformer2DModel (mixgrpo_amd) runs on an MI355X only; there is no CPU path")
         self.store = ParamStore(self.cfg, dev)
+        self.arch = self.store.arch               # arch.describe(cfg): every Linear's shape and place in the flat buffers
         # one flat fp32 parameter (what optimizers / clip_grad_norm_ see); named views via state_dict()
         self.flat_param = torch.nn.Parameter(self.store.w32, requires_grad=True)
         self._work: Dict[Tuple[int, int], _Work] = {}
@@ -411,6 +346,14 @@ class FluxTransformer2DModel(torch.nn.Module):
     def W32(self, name):
         return self.store.view(self.store.w32, name)
 
+    def Wb(self, lin):
+        """(weight, bias) of an `arch.Linear` in the bf16 compute copy."""
+        return self.store.weight(self.store.w16, lin), self.store.bias(self.store.w16, lin)
+
+    def _linear(self, A, lin, C, epi=ops.EPI_BIAS, **kw):
+        """C = epi(A @ W^T + b) of the `arch.Linear` `lin` (A, C: `Rows`)."""
+        ops.gemm(A, *self.Wb(lin), C, lin.N, lin.K, epi, **kw)
+
     def clip_grad_norm_(self, max_norm):
         """Global L2 norm of the fp32 gradients, scaled in place like torch's clip_grad_norm_ (reference :606)."""
         g = self.trainable_store.ensure_grad()
@@ -481,26 +424,25 @@ class FluxTransformer2DModel(torch.nn.Module):
         else:
             ops.attn_fwd(w.Q, w.K, w.Vt, O, lse, w.B, H, w.S, w.Sp, ldo, o_bstride, scale)
 
-    def _qkv_nograd(self, nrm, first, qkv, w, rows, s0, wq, wk, cos, sin):
+    def _qkv_nograd(self, nrm, lin, qkv, w, rows, s0, wq, wk, cos, sin):
         """Fused q | k | v projection of one stream ([tokens, d] -> `qkv` [tokens, 3d]) + QK-norm / RoPE / head split for a
         forward that keeps nothing (the rollout).  When the persistent GEMM takes the shapes: the value projection is issued
         with the operand roles swapped and lands transposed in `w.Vt` [B, H, 128, Sp] at sequence offset `s0`
         (`mgx_linear_bf16_t`), and the q | k projection normalises, rotates and head-splits its tile in the epilogue
         (`mgx_linear_qk_norm_rope`: `qkv` is not touched at all).  Otherwise the plain projection(s) and the norm pass."""
         d, H = self.cfg.dim, self.cfg.num_attention_heads
-        Wf = self.store.fused(self.store.w16, f"{first}.weight", 3 * d)
-        bf = self.store.fused(self.store.w16, f"{first}.bias", 3 * d)
+        qk, v = lin.rows(0, 2 * d), lin.rows(2 * d, 3 * d)
         tokens = nrm.numel() // d
         B = tokens // rows
-        vt = ops.LINEAR_VT and ops.linear_t(nrm, Wf[2 * d:], bf[2 * d:], w.Vt.view(-1)[s0:], tokens, d, d, w.Sp, rows, d * w.Sp)
+        vt = ops.LINEAR_VT and ops.linear_t(nrm, *self.Wb(v), w.Vt.view(-1)[s0:], tokens, d, d, w.Sp, rows, d * w.Sp)
         if vt and ops.LINEAR_QKNORM and H * 128 == d and ops.linear_qk_norm_rope(
-                nrm, Wf[:2 * d], bf[:2 * d], wq, wk, cos, sin, w.Q, w.K, B, H, w.S, rows, s0, d, q_scale=self.q_scale(),
+                nrm, *self.Wb(qk), wq, wk, cos, sin, w.Q, w.K, B, H, w.S, rows, s0, d, q_scale=self.q_scale(),
                 pairs=self._rope_pairs(cos, sin)):
             return
         if vt:
-            ops.gemm(Rows.of(nrm), Wf[:2 * d], bf[:2 * d], Rows(qkv, tokens, 3 * d), 2 * d, d)
+            self._linear(Rows.of(nrm), qk, Rows(qkv, tokens, 3 * d))
         else:
-            ops.gemm(Rows.of(nrm), Wf, bf, Rows.of(qkv), 3 * d, d)
+            self._linear(Rows.of(nrm), lin, Rows.of(qkv))
         ops.qk_norm_rope(qkv, wq, wk, cos, sin, w.Q, w.K, None if vt else w.Vt, B, H, w.S, w.Sp, rows, s0, q_scale=self.q_scale())
 
     def q_scale(self):
@@ -542,30 +484,31 @@ class FluxTransformer2DModel(torch.nn.Module):
         gd = (gd.to(BF16) * 1000).float()
         gd = gd.expand(B).contiguous() if gd.numel() == 1 else gd.contiguous()
 
-        def mlp(name, x, K):
+        emb = {name: (l1, l2) for name, l1, l2 in self.arch.embedders}
+
+        def mlp(name, x):
+            l1, l2 = emb[name]
             h1 = torch.empty(B, d, dtype=BF16, device=dev)
-            ops.skinny_linear(x, self.W(f"time_text_embed.{name}.linear_1.weight"),
-                              self.W(f"time_text_embed.{name}.linear_1.bias"), h1, d, K)
+            ops.skinny_linear(x, *self.Wb(l1), h1, d, l1.K)
             a1 = torch.empty_like(h1)
             ops.ew(h1, None, a1, 0)
             h2 = torch.empty_like(h1)
-            ops.skinny_linear(a1, self.W(f"time_text_embed.{name}.linear_2.weight"),
-                              self.W(f"time_text_embed.{name}.linear_2.bias"), h2, d, d)
+            ops.skinny_linear(a1, *self.Wb(l2), h2, d, d)
             if keep is not None:
                 keep[name] = (x, h1, a1)
             return h2
 
         te = torch.empty(B, 256, dtype=BF16, device=dev)
         ops.sincos_embed(t, te)
-        temb = mlp("timestep_embedder", te, 256)
+        temb = mlp("timestep_embedder", te)
         if self.cfg.guidance_embeds:
             ge = torch.empty(B, 256, dtype=BF16, device=dev)
             ops.sincos_embed(gd, ge)
-            gemb = mlp("guidance_embedder", ge, 256)
+            gemb = mlp("guidance_embedder", ge)
             t2 = torch.empty_like(temb)
             ops.ew(temb, gemb, t2, 2)
             temb = t2
-        pe = mlp("text_embedder", pooled.to(BF16).contiguous(), self.cfg.pooled_projection_dim)
+        pe = mlp("text_embedder", pooled.to(BF16).contiguous())
         t3 = torch.empty_like(temb)
         ops.ew(temb, pe, t3, 2)
         st = torch.empty_like(t3)
@@ -578,100 +521,86 @@ class FluxTransformer2DModel(torch.nn.Module):
             return Rows(t, w.B * w.L, width, w.L, w.S * width)
         return Rows(t[0, w.L:], w.B * w.N, width, w.N, w.S * width)
 
-    def _streams(self, w):
-        """The two streams of a double block as (name, norm, q | k | v projections, norm_q, norm_k, out projection, ff, rows per
-        batch, first sequence row), and each stream's rows of the stacked scratch buffers (nrm / qkv / hid / kept activations).
-        Text first: its rows come first in those buffers and in the joint [B, S, d] residual buffer, and its weights first in
-        the parameter store."""
-        streams = (("txt", "norm1_context", ("add_q_proj", "add_k_proj", "add_v_proj"), "norm_added_q", "norm_added_k",
-                    "to_add_out", "ff_context", w.L, 0),
-                   ("img", "norm1", ("to_q", "to_k", "to_v"), "norm_q", "norm_k", "to_out.0", "ff", w.N, w.L))
-        return streams, {"txt": slice(0, w.B * w.L), "img": slice(w.B * w.L, w.B * w.S)}
+    def _stream_spans(self, w):
+        """What the workspace view decides about the streams of a double block (`arch.Stream`), by stream name: its rows of the
+        stacked scratch buffers (nrm / qkv / hid / kept activations; text first), its rows per batch, its first sequence row."""
+        return ({"txt": slice(0, w.B * w.L), "img": slice(w.B * w.L, w.B * w.S)}, {"txt": w.L, "img": w.N}, {"txt": 0, "img": w.L})
 
     def _double_block(self, i, w, st, cos, sin, pl, mods_in=None):
         """One pass through double block `i` as its plan `pl` lays it out (flux_backward._BlockPlan: the buffer of every role
         and which steps run).  `mods_in`: the forward's modulations, for a recompute pass."""
-        cfg, d, H = self.cfg, self.cfg.dim, self.cfg.num_attention_heads
-        p = f"transformer_blocks.{i}"
-        B = w.B
-        dev = self.store.device
-        mods = {}
-        streams, sl = self._streams(w)
-        W16, fused = self.W, self.store.fused
+        d, H = self.cfg.dim, self.cfg.num_attention_heads
+        B, mods = w.B, {}
+        streams = self.arch.double[i].streams
+        sl, rows, s0 = self._stream_spans(w)
+        Wb, W32, srows = self.Wb, self.W32, self._stream_rows
         if pl.restore is not None:
             w.X.copy_(pl.restore)                               # full recompute rewrites the residual stream
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
+        for s in streams:
             if mods_in is not None:
-                m = mods_in[name]
+                m = mods_in[s.name]
             else:
-                m = torch.empty(B, 6 * d, dtype=BF16, device=dev)
-                ops.skinny_linear(st, W16(f"{p}.{norm}.linear.weight"), W16(f"{p}.{norm}.linear.bias"), m, 6 * d, d)
-            mods[name] = m
-            ops.ln_modulate(self._stream_rows(pl.x_in, w, name, d), m[:, 0:d], m[:, d:2 * d], 6 * d, pl.nrm1[sl[name]], d)
+                m = torch.empty(B, 6 * d, dtype=BF16, device=self.store.device)
+                ops.skinny_linear(st, *Wb(s.norm), m, 6 * d, d)
+            mods[s.name] = m
+            ops.ln_modulate(srows(pl.x_in, w, s.name, d), m[:, 0:d], m[:, d:2 * d], 6 * d, pl.nrm1[sl[s.name]], d)
         if pl.fused_qkv:
             # no-grad forward (the rollout): V^T straight from the value projection, QK-norm / RoPE in the q | k projection's epilogue
-            for name, _, qkvn, nq, nk, _, _, rows, s0 in streams:
-                self._qkv_nograd(pl.nrm1[sl[name]], f"{p}.attn.{qkvn[0]}", pl.qkv[sl[name]], w, rows, s0,
-                                 self.W32(f"{p}.attn.{nq}.weight"), self.W32(f"{p}.attn.{nk}.weight"), cos, sin)
+            for s in streams:
+                self._qkv_nograd(pl.nrm1[sl[s.name]], s.qkv, pl.qkv[sl[s.name]], w, rows[s.name], s0[s.name],
+                                 W32(s.norm_q.name), W32(s.norm_k.name), cos, sin)
         else:
-            for name, _, qkvn, *_ in (streams if pl.run_qkv else ()):        # the fused QKV projections
-                ops.gemm(Rows.of(pl.nrm1[sl[name]]), fused(self.store.w16, f"{p}.attn.{qkvn[0]}.weight", 3 * d),
-                         fused(self.store.w16, f"{p}.attn.{qkvn[0]}.bias", 3 * d), Rows.of(pl.qkv[sl[name]]), 3 * d, d)
-            for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-                ops.qk_norm_rope(pl.qkv[sl[name]], self.W32(f"{p}.attn.{nq}.weight"), self.W32(f"{p}.attn.{nk}.weight"), cos, sin,
-                                 w.Q, w.K, w.Vt, B, H, w.S, w.Sp, rows, s0, V=pl.V, Qt=pl.Qt, Kt=pl.Kt, q_scale=self.q_scale())
+            for s in (streams if pl.run_qkv else ()):        # the fused QKV projections
+                self._linear(Rows.of(pl.nrm1[sl[s.name]]), s.qkv, Rows.of(pl.qkv[sl[s.name]]))
+            for s in streams:
+                ops.qk_norm_rope(pl.qkv[sl[s.name]], W32(s.norm_q.name), W32(s.norm_k.name), cos, sin, w.Q, w.K, w.Vt, B, H, w.S,
+                                 w.Sp, rows[s.name], s0[s.name], V=pl.V, Qt=pl.Qt, Kt=pl.Kt, q_scale=self.q_scale())
         if pl.run_attn:
             self._attn(w, pl.O, pl.lse, d, w.S * d)
         part = lambda t, name: None if t is None else t[sl[name]]
         if pl.run_out:
             # attention output projections, both streams: x += gate_msa * (O @ W^T + b)
-            for name, _, _, _, _, outn, *_ in streams:
-                ops.gemm(self._stream_rows(pl.O, w, name, d), W16(f"{p}.attn.{outn}.weight"), W16(f"{p}.attn.{outn}.bias"),
-                         self._stream_rows(w.X, w, name, d), d, d, EPI_BIAS_GATE_RES, gate=mods[name][:, 2 * d:3 * d],
-                         gate_ld=6 * d, aux=part(pl.y_attn, name))
+            for s in streams:
+                self._linear(srows(pl.O, w, s.name, d), s.out, srows(w.X, w, s.name, d), EPI_BIAS_GATE_RES,
+                             gate=mods[s.name][:, 2 * d:3 * d], gate_ld=6 * d, aux=part(pl.y_attn, s.name))
             if pl.x_mid is not None:
                 pl.x_mid.copy_(w.X)
         x_mid = w.X if pl.run_out else pl.x_mid                  # replay: kept, the residual stream is not written
-        for name in ("txt", "img"):
-            m = mods[name]
-            ops.ln_modulate(self._stream_rows(x_mid, w, name, d), m[:, 3 * d:4 * d], m[:, 4 * d:5 * d], 6 * d, pl.nrm2[sl[name]], d)
+        for s in streams:
+            m = mods[s.name]
+            ops.ln_modulate(srows(x_mid, w, s.name, d), m[:, 3 * d:4 * d], m[:, 4 * d:5 * d], 6 * d, pl.nrm2[sl[s.name]], d)
         # (pre-activation kept: no GEMM in the replay, and no activation either -- its only reader in the backward, the weight
         # gradient of ff.net.2, applies GELU inside its operand transpose: flux_backward._wgrad)
-        for name, _, _, _, _, _, ffn, *_ in (streams if pl.run_ff else ()):
-            ops.gemm(Rows.of(pl.nrm2[sl[name]]), W16(f"{p}.{ffn}.net.0.proj.weight"), W16(f"{p}.{ffn}.net.0.proj.bias"),
-                     Rows.of(w.hid[sl[name]]), 4 * d, d, EPI_BIAS_GELU, aux=part(pl.hid_pre, name))
-        for name, _, _, _, _, _, ffn, *_ in (streams if pl.run_out else ()):
-            ops.gemm(Rows.of(w.hid[sl[name]]), W16(f"{p}.{ffn}.net.2.weight"), W16(f"{p}.{ffn}.net.2.bias"),
-                     self._stream_rows(w.X, w, name, d), d, 4 * d, EPI_BIAS_GATE_RES, gate=mods[name][:, 5 * d:6 * d],
-                     gate_ld=6 * d, aux=part(pl.y_ff, name))
+        for s in (streams if pl.run_ff else ()):
+            self._linear(Rows.of(pl.nrm2[sl[s.name]]), s.ff0, Rows.of(w.hid[sl[s.name]]), EPI_BIAS_GELU, aux=part(pl.hid_pre, s.name))
+        for s in (streams if pl.run_out else ()):
+            self._linear(Rows.of(w.hid[sl[s.name]]), s.ff2, srows(w.X, w, s.name, d), EPI_BIAS_GATE_RES,
+                         gate=mods[s.name][:, 5 * d:6 * d], gate_ld=6 * d, aux=part(pl.y_ff, s.name))
         return mods
 
     def _single_block(self, i, w, st, cos, sin, pl, mod_in=None):
         """As `_double_block`.  [O | mlp] lives in `w.cat` at row stride 5d, except in a lean replay (`pl.lean`), which builds
         no such operand."""
-        cfg, d, H = self.cfg, self.cfg.dim, self.cfg.num_attention_heads
-        p = f"single_transformer_blocks.{i}"
-        B, S = w.B, w.S
-        M = B * S
+        d, H = self.cfg.dim, self.cfg.num_attention_heads
+        blk, Wb = self.arch.single[i], self.Wb
+        B, S, M = w.B, w.S, w.B * w.S
         if pl.restore is not None:
             w.X.copy_(pl.restore)
         if mod_in is not None:
             m = mod_in
         else:
             m = torch.empty(B, 3 * d, dtype=BF16, device=self.store.device)
-            ops.skinny_linear(st, self.W(f"{p}.norm.linear.weight"), self.W(f"{p}.norm.linear.bias"), m, 3 * d, d)
+            ops.skinny_linear(st, *Wb(blk.norm), m, 3 * d, d)
         Xa = Rows(pl.x_in, M, d, S, S * d)
         ops.ln_modulate(Xa, m[:, 0:d], m[:, d:2 * d], 3 * d, pl.nrm1, d)
-        wq, wk = self.W32(f"{p}.attn.norm_q.weight"), self.W32(f"{p}.attn.norm_k.weight")
+        wq, wk = self.W32(blk.norm_q.name), self.W32(blk.norm_k.name)
         if pl.fused_qkv:
-            self._qkv_nograd(pl.nrm1, f"{p}.attn.to_q", pl.qkv, w, S, 0, wq, wk, cos, sin)
+            self._qkv_nograd(pl.nrm1, blk.qkv, pl.qkv, w, S, 0, wq, wk, cos, sin)
         elif pl.run_qkv:
-            ops.gemm(Rows.of(pl.nrm1), self.store.fused(self.store.w16, f"{p}.attn.to_q.weight", 3 * d),
-                     self.store.fused(self.store.w16, f"{p}.attn.to_q.bias", 3 * d), Rows.of(pl.qkv), 3 * d, d)
+            self._linear(Rows.of(pl.nrm1), blk.qkv, Rows.of(pl.qkv))
         cat2 = w.cat.view(M, 5 * d)
         if pl.run_ff:
-            ops.gemm(Rows.of(pl.nrm1), self.W(f"{p}.proj_mlp.weight"), self.W(f"{p}.proj_mlp.bias"),
-                     Rows(cat2[0, d:], M, 5 * d), 4 * d, d, EPI_BIAS_GELU, aux=pl.hid_pre)
+            self._linear(Rows.of(pl.nrm1), blk.proj_mlp, Rows(cat2[0, d:], M, 5 * d), EPI_BIAS_GELU, aux=pl.hid_pre)
         if not pl.fused_qkv:
             ops.qk_norm_rope(pl.qkv, wq, wk, cos, sin, w.Q, w.K, w.Vt, B, H, S, w.Sp, S, 0, V=pl.V, Qt=pl.Qt, Kt=pl.Kt,
                              q_scale=self.q_scale())
@@ -682,8 +611,7 @@ class FluxTransformer2DModel(torch.nn.Module):
         elif not pl.lean:
             w.cat[:, :, :d].copy_(pl.O_keep)         # (the wgrad of proj_out then reads [O | mlp] as one [M, 5d] operand)
         if pl.run_out:
-            ops.gemm(Rows.of(cat2), self.W(f"{p}.proj_out.weight"), self.W(f"{p}.proj_out.bias"), Xa, d, 5 * d,
-                     EPI_BIAS_GATE_RES, gate=m[:, 2 * d:3 * d], gate_ld=3 * d, aux=pl.y_attn)
+            self._linear(Rows.of(cat2), blk.proj_out, Xa, EPI_BIAS_GATE_RES, gate=m[:, 2 * d:3 * d], gate_ld=3 * d, aux=pl.y_attn)
         return m
 
     def _embed(self, w, hidden_states, encoder_hidden_states):
@@ -694,23 +622,21 @@ class FluxTransformer2DModel(torch.nn.Module):
             w.in16.copy_(hs.reshape(B * N, -1))
         else:
             ops.cast_bf16(hs.to(F32).contiguous().view(-1), w.in16.view(-1))
-        ops.gemm(Rows.of(w.in16), self.W("x_embedder.weight"), self.W("x_embedder.bias"),
-                 self._stream_rows(w.X, w, "img", d), d, self.cfg.in_channels)
+        self._linear(Rows.of(w.in16), self.arch.x_embedder, self._stream_rows(w.X, w, "img", d))
         ehs = encoder_hidden_states.detach().to(BF16).contiguous()
-        ops.gemm(Rows.of(ehs.view(B * L, -1)), self.W("context_embedder.weight"), self.W("context_embedder.bias"),
-                 self._stream_rows(w.X, w, "txt", d), d, self.cfg.joint_attention_dim)
+        self._linear(Rows.of(ehs.view(B * L, -1)), self.arch.context_embedder, self._stream_rows(w.X, w, "txt", d))
         return ehs
 
     def _head(self, w, st):
         d = self.cfg.dim
         B, N = w.B, w.N
         e = torch.empty(B, 2 * d, dtype=BF16, device=self.store.device)
-        ops.skinny_linear(st, self.W("norm_out.linear.weight"), self.W("norm_out.linear.bias"), e, 2 * d, d)
+        ops.skinny_linear(st, *self.Wb(self.arch.norm_out), e, 2 * d, d)
         nrm = w.nrm[:B * N]
         ops.ln_modulate(self._stream_rows(w.X, w, "img", d), e[:, d:2 * d], e[:, 0:d], 2 * d, nrm, d)   # scale first
-        cout = self.cfg.patch_size * self.cfg.patch_size * self.cfg.in_channels
+        cout = self.arch.proj_out.N
         out = torch.empty(B, N, cout, dtype=BF16, device=self.store.device)
-        ops.gemm(Rows.of(nrm), self.W("proj_out.weight"), self.W("proj_out.bias"), Rows.of(out.view(B * N, cout)), cout, d)
+        self._linear(Rows.of(nrm), self.arch.proj_out, Rows.of(out.view(B * N, cout)))
         return out, e
 
     def forward(self, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections, img_ids,

@@ -9,14 +9,13 @@ buffer (MGX_EPI_F32_ACC, beta = 1); activation gradients are bf16 like autograd'
 All arithmetic is in csrc/ kernels; this file only sequences them.
 """
 import math
+import os
 
 import torch
 
 from . import ops
-from .ops import BF16, F32, Rows, EPI_BIAS, EPI_BIAS_GATE_RES, EPI_DGELU, EPI_F32_ACC
-
-
-import os
+from ._lib import MgxError
+from .ops import BF16, F32, Rows, EPI_BIAS, EPI_DGELU, EPI_F32_ACC
 
 KEEP_ACTS = os.environ.get("MGX_KEEP_ACTS", "1") != "0"
 # How many blocks ALSO keep their FF / proj_mlp pre-activation ([M, 4d] bf16 per block: 0.79 GB at micro-batch 7), so that the
@@ -63,8 +62,7 @@ class _Train:
                 if b < cfg.num_layers:
                     k.update(y_ff=e(M, d), x_mid=e(B, S, d))
                 self.keep.append(k)
-            self._ff_shape, self._ff_device = (M, 4 * d), device
-            self._qkv_shape = (M, 3 * d)
+            self._grow_shape, self._device = {"hid_pre": (M, 4 * d), "qkv": (M, 3 * d)}, device
             if KEEP_FF != "auto":
                 self.grow_ff(int(KEEP_FF))
             if KEEP_QKV != "auto":
@@ -88,52 +86,39 @@ class _Train:
     def view(self, B):
         return self if B == self.B else _TrainView(self, B)
 
-    def ff_block_bytes(self):
-        return self._ff_shape[0] * self._ff_shape[1] * 2
-
     def ff_kept(self):
         return sum(1 for k in (self.keep or []) if "hid_pre" in k)
-
-    def qkv_block_bytes(self):
-        return self._qkv_shape[0] * self._qkv_shape[1] * 2
 
     def qkv_kept(self):
         return sum(1 for k in (self.keep or []) if "qkv" in k)
 
+    def _grow(self, blocks, names, budget_bytes=math.inf):
+        """Allocate the keep buffers `names` ("hid_pre": the FF pre-activation, "qkv": the QKV projection's output) that
+        `blocks` lack, block by block, while `budget_bytes` covers the next one.  Returns the bytes left."""
+        for k in blocks:
+            for name in (n for n in names if n not in k):
+                size = math.prod(self._grow_shape[name]) * 2
+                if budget_bytes < size:
+                    return budget_bytes
+                k[name] = torch.empty(*self._grow_shape[name], dtype=BF16, device=self._device)
+                budget_bytes -= size
+        return budget_bytes
+
     def grow_ff(self, n_total):
         """Keep the FF pre-activation of the first `n_total` blocks (allocates the missing buffers)."""
-        if self.keep is None:
-            return 0
-        for k in self.keep[:max(0, n_total)]:
-            if "hid_pre" not in k:
-                k["hid_pre"] = torch.empty(*self._ff_shape, dtype=BF16, device=self._ff_device)
+        self._grow((self.keep or [])[:max(0, n_total)], ("hid_pre",))
         return self.ff_kept()
 
     def grow_qkv(self, n_total):
         """Keep the QKV projection's output of the first `n_total` blocks (allocates the missing buffers)."""
-        if self.keep is None:
-            return 0
-        for k in self.keep[:max(0, n_total)]:
-            if "qkv" not in k:
-                k["qkv"] = torch.empty(*self._qkv_shape, dtype=BF16, device=self._ff_device)
+        self._grow((self.keep or [])[:max(0, n_total)], ("qkv",))
         return self.qkv_kept()
 
     def grow_auto(self, budget_bytes):
         """Spend `budget_bytes` block by block, FF pre-activation before QKV output, on whatever is still recomputed and
         set to "auto".  Returns the bytes left."""
-        if self.keep is None:
-            return budget_bytes
-        for i, k in enumerate(self.keep):
-            for name, auto, size, grow in (("hid_pre", KEEP_FF == "auto", self.ff_block_bytes(), self.grow_ff),
-                                           ("qkv", KEEP_QKV == "auto", self.qkv_block_bytes(), self.grow_qkv)):
-                if name in k or not auto:
-                    continue
-                if budget_bytes < size:
-                    return budget_bytes
-                k[name] = torch.empty(*(self._ff_shape if name == "hid_pre" else self._qkv_shape), dtype=BF16,
-                                      device=self._ff_device)
-                budget_bytes -= size
-        return budget_bytes
+        auto = tuple(n for n, mode in (("hid_pre", KEEP_FF), ("qkv", KEEP_QKV)) if mode == "auto")
+        return self._grow(self.keep or [], auto, budget_bytes)
 
 
 class _TrainView:
@@ -262,7 +247,6 @@ class FluxFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         if getattr(ctx.w.train, "generation", None) != ctx.generation:
-            from ._lib import MgxError
             raise MgxError("FluxTransformer2DModel: the activations of this forward pass were overwritten by a later "
                            "grad-enabled forward of the same model (one pending backward per model; call backward() "
                            "before the next training forward)")
@@ -276,48 +260,42 @@ class FluxFunction(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------ helpers
-def _wgrad(model, tr, A, K, dC: Rows, N, wname, bname, rows=None):
-    """g32[W] += dC^T A ; g32[b] += colsum(dC).  `rows`: number of fused weight rows when W spans several tensors.
+def _wgrad(model, tr, lin, A, dC: Rows):
+    """g32[W] += dC^T A ; g32[b] += colsum(dC) for the `arch.Linear` `lin` (a fused one: all its members' rows at once).
     `A`: the [M, K] activation as `Rows`, or a list of column blocks `(Rows, width, gelu)` that make it up side by side --
     `gelu`: that block is gelu_tanh of the given (kept) pre-activation, applied on the way into the transposed operand.
-    With adapters attached (model.lora): the rank-r gradients of the targets among these rows, nothing for frozen tensors."""
+    With adapters attached (model.lora): the rank-r gradients of the targets among `lin`'s members, nothing for frozen tensors."""
     if model.lora is not None:
-        return _lora_wgrad(model, A, K, dC, wname, N if rows else None)
-    st = model.store
+        return _lora_wgrad(model, lin, A, dC)
+    st, N, K = model.store, lin.N, lin.K
     g = st.ensure_grad()
     parts = A if isinstance(A, list) else [(A, K, False)]
-    M = parts[0][0].M
-    Mp = _pad64(M)
+    Mp = _pad64(parts[0][0].M)
     dCt = tr.dCt[:N * Mp].view(N, Mp)
     At = tr.At[:K * Mp].view(K, Mp)
-    gb = None
-    if bname is not None:
-        gb = st.fused(g, bname, N) if rows else st.view(g, bname)
-    ops.transpose(dC, N, dCt, Mp, colsum_out=gb, colsum_beta=1.0)
+    ops.transpose(dC, N, dCt, Mp, colsum_out=st.bias(g, lin), colsum_beta=1.0)
     k0 = 0
     for a_rows, width, gelu in parts:
         ops.transpose(a_rows, width, At[k0:k0 + width], Mp, gelu=gelu)
         k0 += width
     assert k0 == K
-    gw = st.fused(g, wname, N) if rows else st.view(g, wname)
-    ops.gemm(Rows.of(dCt), At, None, Rows(gw, N, K), K, Mp, EPI_F32_ACC, beta=1.0, ldw=Mp)
+    ops.gemm(Rows.of(dCt), At, None, Rows(st.weight(g, lin), N, K), K, Mp, EPI_F32_ACC, beta=1.0, ldw=Mp)
 
 
-def _lora_wgrad(model, X, K, dC: Rows, wname, rows_total):
-    """The low-rank branch of `_wgrad`: for every adapter target among the weight rows of this call (the members of a fused
-    projection are column slices of dC), with s = alpha / r:
+def _lora_wgrad(model, lin, X, dC: Rows):
+    """The low-rank branch of `_wgrad`: for every adapter target among `lin`'s members (the members of a fused projection
+    are column slices of dC), with s = alpha / r:
         T = bf16(s X A^T) [M, r];  dT = bf16(s dC B) [M, r];  g[Bt] += T^T dC;  g[A] += dT^T X      (fp32 accumulation)
     The full dW is never formed; bias gradients are not computed (frozen)."""
     lo = model.lora
-    members = lo.members(wname, rows_total)
+    members = lo.members(lin)
     if not members:
         return
     assert isinstance(X, Rows), "adapter targets take their input as one row-batched matrix"
     g = lo.ensure_grad()
-    r, M = lo.rank, dC.M
-    dev = lo.device
-    T = ops.scratch("lora_T", M * r, BF16, dev)
-    dT = ops.scratch("lora_dT", M * r, BF16, dev)
+    r, M, K = lo.rank, dC.M, lin.K
+    T = ops.scratch("lora_T", M * r, BF16, lo.device)
+    dT = ops.scratch("lora_dT", M * r, BF16, lo.device)
     flat = dC.t.reshape(-1)
     for module, col, n in members:
         A16, Bt16 = lo.view(lo.w16, f"{module}.lora_A"), lo.view(lo.w16, f"{module}.lora_Bt")
@@ -328,15 +306,16 @@ def _lora_wgrad(model, X, K, dC: Rows, wname, rows_total):
         ops.lora_wgrad(dT, X, lo.view(g, f"{module}.lora_A"), K, r, beta=1.0)
 
 
-def _dgrad(model, tr, dC: Rows, N, K, wname, out: Rows, rows=None, epi=EPI_BIAS, aux=None, ldaux=None, row_lo=0,
-           row_hi=None, gate=None):
-    """out[M, K'] = epi(dC[M, N] @ W[N, K][:, row_lo:row_hi]) via a transposed copy of W (K-contiguous operand)."""
-    st = model.store
-    W = st.fused(st.w16, wname, N) if rows else st.view(st.w16, wname)
-    Wt = tr.Wt[:K * N].view(K, N)
-    ops.transpose(Rows.of(W), K, Wt, N)
-    row_hi = K if row_hi is None else row_hi
-    ops.gemm(dC, Wt[row_lo:row_hi], None, out, row_hi - row_lo, N, epi, aux=aux, ldaux=ldaux, gate=gate, gate_ld=0)
+def _weight_t(model, tr, lin):
+    """W^T [K, N] of `lin`'s bf16 weight, written into tr.Wt: the K-contiguous operand of the input-gradient GEMMs."""
+    Wt = tr.Wt[:lin.K * lin.N].view(lin.K, lin.N)
+    ops.transpose(Rows.of(model.store.weight(model.store.w16, lin)), lin.K, Wt, lin.N)
+    return Wt
+
+
+def _dgrad(model, tr, lin, dC: Rows, out: Rows, epi=EPI_BIAS, aux=None, ldaux=None, gate=None):
+    """out[M, K] = epi(dC[M, N] @ W[N, K])."""
+    ops.gemm(dC, _weight_t(model, tr, lin), None, out, lin.K, lin.N, epi, aux=aux, ldaux=ldaux, gate=gate, gate_ld=0)
 
 
 def _attn_bwd(model, w, Q, K, V, Qt, Kt, O, dO, lse, tr, B, H, S, Sp, ldo, o_bstride, scale):
@@ -352,66 +331,60 @@ def _attn_bwd(model, w, Q, K, V, Qt, Kt, O, dO, lse, tr, B, H, S, Sp, ldo, o_bst
         ops.attn_bwd(Q, K, V, Qt, Kt, O, dO, lse, tr.delta, tr.dOt, tr.dQ, tr.dK, tr.dV, B, H, S, Sp, ldo, o_bstride, scale)
     elif not ops.attn_bwd_kv(Q, K, V, Qt, Kt, O, dO, lse, tr.delta, tr.dOt, tr.dQ, tr.dK, tr.dV, B, H, S, w.kv_len, ldo, o_bstride,
                              scale):
-        from ._lib import MgxError
         raise MgxError(f"mgx_attn_bwd_kv refused B {B} H {H} Sa {S} kv_len {w.kv_len} after its path query took it")
 
 
-def _skinny_bwd(model, tr, dmod, x, wname, bname, N, K, dx_acc):
+def _skinny_bwd(model, tr, lin, dmod, x, dx_acc):
     """Modulation / embedder linear backward: g32[W] += dmod^T x, g32[b] += sum_b dmod, dx_acc += dmod @ W.  With adapters
     attached these weights are frozen: only the input-gradient half runs."""
     st = model.store
     if model.lora is None:
         g = st.ensure_grad()
-        ops.skinny_wgrad(dmod, x, st.view(g, wname), st.view(g, bname), N, K)
+        ops.skinny_wgrad(dmod, x, st.weight(g, lin), st.bias(g, lin), lin.N, lin.K)
     if dx_acc is not None:
-        ops.skinny_dgrad(dmod, st.view(st.w16, wname), dx_acc, N, K)      # straight from the row-major weight
+        ops.skinny_dgrad(dmod, st.weight(st.w16, lin), dx_acc, lin.N, lin.K)      # straight from the row-major weight
 
 
 def _backward(model, w, tr, sv, dout):
-    cfg = model.cfg
+    cfg, arch = model.cfg, model.arch
     d, H = cfg.dim, cfg.num_attention_heads
     B, L, N, S, Sp = w.B, w.L, w.N, w.S, w.Sp
     M = B * S
-    dev = model.store.device
+    dev, store = model.store.device, model.store
     st_, cos, sin = sv["st"], sv["cos"], sv["sin"]
     scale, q_scale = model.attn_scale(), model.q_scale()   # (ln 2, scale * log2 e) for the prescaled Q of mgx_attn_fwd_log2
-    store = model.store
     if model.lora is None:
         g32 = store.ensure_grad()
-        gnorm = lambda name: store.view(g32, name)
+        gnorm = lambda vec: store.view(g32, vec.name)
     else:
         # the RMSNorm weights are frozen; mgx_qk_norm_rope_bwd_qs still accumulates their gradients somewhere: a sink
         sink = torch.zeros(cfg.attention_head_dim, dtype=F32, device=dev)
-        gnorm = lambda name: sink
+        gnorm = lambda vec: sink
     dst = torch.zeros(B, d, dtype=BF16, device=dev)        # grad wrt st = silu(temb), summed over all users
 
-    def srows(t, which, width):
-        return model._stream_rows(t, w, which, width)
+    srows = lambda t, which, width: model._stream_rows(t, w, which, width)
 
     # ---------------- head: out = proj_out( LN(x_img) * (1+scale) + shift )
-    cout = cfg.patch_size * cfg.patch_size * cfg.in_channels
     e = sv["e"]
     nrm = tr.save["nrm1"][:B * N]
     ops.ln_modulate(srows(tr.x_final, "img", d), e[:, d:2 * d], e[:, 0:d], 2 * d, nrm, d)
-    dC = Rows.of(dout.view(B * N, cout))
-    _wgrad(model, tr, Rows.of(nrm), d, dC, cout, "proj_out.weight", "proj_out.bias")
+    dC = Rows.of(dout.view(B * N, arch.proj_out.N))
+    _wgrad(model, tr, arch.proj_out, Rows.of(nrm), dC)
     dn = tr.dnrm[:B * N]
-    _dgrad(model, tr, dC, cout, d, "proj_out.weight", Rows.of(dn))
+    _dgrad(model, tr, arch.proj_out, dC, Rows.of(dn))
     tr.dX.zero_()
     de = torch.zeros(B, 2 * d, dtype=BF16, device=dev)
     ops.ln_modulate_bwd(dn, srows(tr.x_final, "img", d), e[:, 0:d], 2 * d, srows(tr.dX, "img", d), False,
                         de[:, d:2 * d], de[:, 0:d], d)
-    _skinny_bwd(model, tr, de, st_, "norm_out.linear.weight", "norm_out.linear.bias", 2 * d, d, dst)
+    _skinny_bwd(model, tr, arch.norm_out, de, st_, dst)
 
     # data-parallel overlap (dist_utils.GradReducer): set by the trainer for the LAST micro-batch before an optimizer step;
     # called with a block's prefix once every gradient of that block is final
     grad_ready = getattr(model, "_grad_ready", None) or (lambda prefix: None)
     grad_ready("tail")
-    nblk = cfg.num_layers + cfg.num_single_layers
     # ---------------- single blocks (reverse)
     for i in reversed(range(cfg.num_single_layers)):
-        blk = cfg.num_layers + i
-        p = f"single_transformer_blocks.{i}"
+        blk, sb = cfg.num_layers + i, arch.single[i]
         m = sv["mods"][blk]
         pl = _BlockPlan(w, False, tr, blk, recompute=True)
         model._single_block(i, w, st_, cos, sin, pl, mod_in=m)
@@ -425,102 +398,88 @@ def _backward(model, w, tr, sv, dout):
         # gradient of proj_out takes O from its keep buffer and gelu(hid_pre) formed inside the transpose, and the attention
         # backward reads O / writes dO at row stride d instead of 5d
         a_op = [(Rows.of(pl.O.view(M, d)), d, False), (Rows.of(pl.hid_pre), 4 * d, True)] if pl.lean else Rows.of(pl.O.view(M, 5 * d))
-        _wgrad(model, tr, a_op, 5 * d, dyr, d, f"{p}.proj_out.weight", f"{p}.proj_out.bias")
+        _wgrad(model, tr, sb.proj_out, a_op, dyr)
         dO = tr.dO.view(-1)[:M * pl.ldo].view(B, S, pl.ldo)    # d(cat) [B, S, 5d]; lean: dO alone, [B, S, d]
         dbig = tr.dbig                                         # [M, 7d] = [dq | dk | dv | dmlp_pre]
-        # d(cat)[:, :d] = dO (attention output grad) ; d(cat)[:, d:] -> through GELU -> dbig[:, 3d:]
-        stW = store.view(store.w16, f"{p}.proj_out.weight")
-        Wt = tr.Wt[:5 * d * d].view(5 * d, d)
-        ops.transpose(Rows.of(stW), 5 * d, Wt, d)
+        # one transpose of proj_out, two GEMMs: d(cat)[:, :d] = dO (attention output grad) ; d(cat)[:, d:] -> through GELU -> dbig[:, 3d:]
+        Wt = _weight_t(model, tr, sb.proj_out)
         ops.gemm(dyr, Wt[0:d], None, Rows.of(dO.view(M, pl.ldo)), d, d, EPI_BIAS)
         ops.gemm(dyr, Wt[d:5 * d], None, Rows(dbig[0, 3 * d:], M, 7 * d), 4 * d, d, EPI_DGELU, aux=pl.hid_pre, ldaux=4 * d)
         _attn_bwd(model, w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO, pl.lse, tr, B, H, S, Sp, pl.ldo, S * pl.ldo, scale)
         # qk norm / rope backward writes [dq|dk|dv] straight into columns 0..3d of the [M, 7d] staging matrix
-        ops.qk_norm_rope_bwd(pl.qkv, model.W32(f"{p}.attn.norm_q.weight"), model.W32(f"{p}.attn.norm_k.weight"), cos, sin,
-                             tr.dQ, tr.dK, tr.dV, dbig, gnorm(f"{p}.attn.norm_q.weight"),
-                             gnorm(f"{p}.attn.norm_k.weight"), B, H, S, Sp, S, 0, ld_dqkv=7 * d, q_scale=q_scale)
+        ops.qk_norm_rope_bwd(pl.qkv, model.W32(sb.norm_q.name), model.W32(sb.norm_k.name), cos, sin, tr.dQ, tr.dK, tr.dV, dbig,
+                             gnorm(sb.norm_q), gnorm(sb.norm_k), B, H, S, Sp, S, 0, ld_dqkv=7 * d, q_scale=q_scale)
         dbr = Rows.of(dbig)
-        _wgrad(model, tr, Rows.of(pl.nrm1), d, dbr, 7 * d, f"{p}.attn.to_q.weight", f"{p}.attn.to_q.bias", rows=True)
-        _dgrad(model, tr, dbr, 7 * d, d, f"{p}.attn.to_q.weight", Rows.of(tr.dnrm), rows=True)
+        _wgrad(model, tr, sb.qkv_mlp, Rows.of(pl.nrm1), dbr)
+        _dgrad(model, tr, sb.qkv_mlp, dbr, Rows.of(tr.dnrm))
         ops.ln_modulate_bwd(tr.dnrm, x_in, m[:, d:2 * d], 3 * d, dXr, True, dmod[:, 0:d], dmod[:, d:2 * d], d)
-        _skinny_bwd(model, tr, dmod, st_, f"{p}.norm.linear.weight", f"{p}.norm.linear.bias", 3 * d, d, dst)
-        grad_ready(p)
+        _skinny_bwd(model, tr, sb.norm, dmod, st_, dst)
+        grad_ready(sb.prefix)
 
     # ---------------- double blocks (reverse)
-    streams, sl = model._streams(w)
+    sl, rows, s0 = model._stream_spans(w)
     dO3 = tr.dO.view(-1)[:B * S * d].view(B, S, d)
     dh_all = tr.dbig.view(-1)[:M * 4 * d].view(M, 4 * d)
     dqkv_all = tr.dbig.view(-1)[:M * 3 * d].view(M, 3 * d)
     for i in reversed(range(cfg.num_layers)):
-        p = f"transformer_blocks.{i}"
+        streams = arch.double[i].streams
         mods = sv["mods"][i]
         pl = _BlockPlan(w, True, tr, i, recompute=True)
         model._double_block(i, w, st_, cos, sin, pl, mods_in=mods)
         dmods = {k: torch.empty(B, 6 * d, dtype=BF16, device=dev) for k in ("img", "txt")}
+        dy = {s.name: Rows.of(tr.dy[sl[s.name]]) for s in streams}
         # ---- FF branch: out = x_mid + gate_mlp * ff2(gelu(ff1(LNmod(x_mid))))
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            m, dm = mods[name], dmods[name]
-            ops.gate_bwd(srows(tr.dX, name, d), pl.y_ff[sl[name]], m[:, 5 * d:6 * d], 6 * d, tr.dy[sl[name]],
-                         dm[:, 5 * d:6 * d], B, rows, d)
+        for s in streams:
+            m, dm, rs = mods[s.name], dmods[s.name], sl[s.name]
+            ops.gate_bwd(srows(tr.dX, s.name, d), pl.y_ff[rs], m[:, 5 * d:6 * d], 6 * d, tr.dy[rs], dm[:, 5 * d:6 * d], B,
+                         rows[s.name], d)
             # (ff.net.0 not run again: the recompute pass formed no activation; gelu(hid_pre) is applied inside the transpose)
-            a_op = Rows.of(w.hid[sl[name]]) if pl.run_ff else [(Rows.of(pl.hid_pre[sl[name]]), 4 * d, True)]
-            _wgrad(model, tr, a_op, 4 * d, Rows.of(tr.dy[sl[name]]), d, f"{p}.{ffn}.net.2.weight", f"{p}.{ffn}.net.2.bias")
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            _dgrad(model, tr, Rows.of(tr.dy[sl[name]]), d, 4 * d, f"{p}.{ffn}.net.2.weight", Rows.of(dh_all[sl[name]]),
-                   epi=EPI_DGELU, aux=pl.hid_pre[sl[name]], ldaux=4 * d)
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            _wgrad(model, tr, Rows.of(pl.nrm2[sl[name]]), d, Rows.of(dh_all[sl[name]]), 4 * d, f"{p}.{ffn}.net.0.proj.weight",
-                   f"{p}.{ffn}.net.0.proj.bias")
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            _dgrad(model, tr, Rows.of(dh_all[sl[name]]), 4 * d, d, f"{p}.{ffn}.net.0.proj.weight", Rows.of(tr.dnrm[sl[name]]))
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            m, dm = mods[name], dmods[name]
-            dXs = srows(tr.dX, name, d)
-            ops.ln_modulate_bwd(tr.dnrm[sl[name]], srows(pl.x_mid, name, d), m[:, 4 * d:5 * d], 6 * d, dXs, True,
+            a_op = Rows.of(w.hid[rs]) if pl.run_ff else [(Rows.of(pl.hid_pre[rs]), 4 * d, True)]
+            _wgrad(model, tr, s.ff2, a_op, dy[s.name])
+        for s in streams:
+            _dgrad(model, tr, s.ff2, dy[s.name], Rows.of(dh_all[sl[s.name]]), epi=EPI_DGELU, aux=pl.hid_pre[sl[s.name]], ldaux=4 * d)
+        for s in streams:
+            _wgrad(model, tr, s.ff0, Rows.of(pl.nrm2[sl[s.name]]), Rows.of(dh_all[sl[s.name]]))
+        for s in streams:
+            _dgrad(model, tr, s.ff0, Rows.of(dh_all[sl[s.name]]), Rows.of(tr.dnrm[sl[s.name]]))
+        for s in streams:
+            m, dm, rs = mods[s.name], dmods[s.name], sl[s.name]
+            dXs = srows(tr.dX, s.name, d)
+            ops.ln_modulate_bwd(tr.dnrm[rs], srows(pl.x_mid, s.name, d), m[:, 4 * d:5 * d], 6 * d, dXs, True,
                                 dm[:, 3 * d:4 * d], dm[:, 4 * d:5 * d], d)
             # ---- attention branch: x_mid = x_in + gate_msa * to_out(O)
-            ops.gate_bwd(dXs, pl.y_attn[sl[name]], m[:, 2 * d:3 * d], 6 * d, tr.dy[sl[name]], dm[:, 2 * d:3 * d], B, rows, d)
-            _wgrad(model, tr, srows(pl.O, name, d), d, Rows.of(tr.dy[sl[name]]), d, f"{p}.attn.{outn}.weight",
-                   f"{p}.attn.{outn}.bias")
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            _dgrad(model, tr, Rows.of(tr.dy[sl[name]]), d, d, f"{p}.attn.{outn}.weight", srows(dO3, name, d))
+            ops.gate_bwd(dXs, pl.y_attn[rs], m[:, 2 * d:3 * d], 6 * d, tr.dy[rs], dm[:, 2 * d:3 * d], B, rows[s.name], d)
+            _wgrad(model, tr, s.out, srows(pl.O, s.name, d), dy[s.name])
+        for s in streams:
+            _dgrad(model, tr, s.out, dy[s.name], srows(dO3, s.name, d))
         _attn_bwd(model, w, w.Q, w.K, pl.V, pl.Qt, pl.Kt, pl.O, dO3, pl.lse, tr, B, H, S, Sp, d, S * d, scale)
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            ops.qk_norm_rope_bwd(pl.qkv[sl[name]], model.W32(f"{p}.attn.{nq}.weight"), model.W32(f"{p}.attn.{nk}.weight"), cos,
-                                 sin, tr.dQ, tr.dK, tr.dV, dqkv_all[sl[name]], gnorm(f"{p}.attn.{nq}.weight"),
-                                 gnorm(f"{p}.attn.{nk}.weight"), B, H, S, Sp, rows, s0, q_scale=q_scale)
-            _wgrad(model, tr, Rows.of(pl.nrm1[sl[name]]), d, Rows.of(dqkv_all[sl[name]]), 3 * d, f"{p}.attn.{qkvn[0]}.weight",
-                   f"{p}.attn.{qkvn[0]}.bias", rows=True)
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            _dgrad(model, tr, Rows.of(dqkv_all[sl[name]]), 3 * d, d, f"{p}.attn.{qkvn[0]}.weight", Rows.of(tr.dnrm[sl[name]]),
-                   rows=True)
-        for name, norm, qkvn, nq, nk, outn, ffn, rows, s0 in streams:
-            m, dm = mods[name], dmods[name]
-            ops.ln_modulate_bwd(tr.dnrm[sl[name]], srows(tr.block_in[i], name, d), m[:, d:2 * d], 6 * d, srows(tr.dX, name, d),
-                                True, dm[:, 0:d], dm[:, d:2 * d], d)
-            _skinny_bwd(model, tr, dm, st_, f"{p}.{norm}.linear.weight", f"{p}.{norm}.linear.bias", 6 * d, d, dst)
-        grad_ready(p)
+        for s in streams:
+            ops.qk_norm_rope_bwd(pl.qkv[sl[s.name]], model.W32(s.norm_q.name), model.W32(s.norm_k.name), cos, sin, tr.dQ, tr.dK,
+                                 tr.dV, dqkv_all[sl[s.name]], gnorm(s.norm_q), gnorm(s.norm_k), B, H, S, Sp, rows[s.name],
+                                 s0[s.name], q_scale=q_scale)
+            _wgrad(model, tr, s.qkv, Rows.of(pl.nrm1[sl[s.name]]), Rows.of(dqkv_all[sl[s.name]]))
+        for s in streams:
+            _dgrad(model, tr, s.qkv, Rows.of(dqkv_all[sl[s.name]]), Rows.of(tr.dnrm[sl[s.name]]))
+        for s in streams:
+            m, dm = mods[s.name], dmods[s.name]
+            ops.ln_modulate_bwd(tr.dnrm[sl[s.name]], srows(tr.block_in[i], s.name, d), m[:, d:2 * d], 6 * d,
+                                srows(tr.dX, s.name, d), True, dm[:, 0:d], dm[:, d:2 * d], d)
+            _skinny_bwd(model, tr, s.norm, dm, st_, dst)
+        grad_ready(arch.double[i].prefix)
 
     # ---------------- embedders (inputs need no gradient)
-    _wgrad(model, tr, Rows.of(sv["in16"]), cfg.in_channels, srows(tr.dX, "img", d), d, "x_embedder.weight",
-           "x_embedder.bias")
-    _wgrad(model, tr, Rows.of(sv["ehs"].view(B * L, -1)), cfg.joint_attention_dim, srows(tr.dX, "txt", d), d,
-           "context_embedder.weight", "context_embedder.bias")
+    _wgrad(model, tr, arch.x_embedder, Rows.of(sv["in16"]), srows(tr.dX, "img", d))
+    _wgrad(model, tr, arch.context_embedder, Rows.of(sv["ehs"].view(B * L, -1)), srows(tr.dX, "txt", d))
 
     # ---------------- temb path: st = silu(temb); temb = sum of three MLP outputs
     dtemb = torch.empty(B, d, dtype=BF16, device=dev)
     ops.ew(sv["temb"], dst, dtemb, 1)
-    for name, (x, h1, a1) in sv["keep"].items():
-        K = x.shape[1]
+    for name, linear_1, linear_2 in arch.embedders:
+        x, h1, a1 = sv["keep"][name]
         da1 = torch.zeros(B, d, dtype=BF16, device=dev)
-        _skinny_bwd(model, tr, dtemb, a1, f"time_text_embed.{name}.linear_2.weight",
-                    f"time_text_embed.{name}.linear_2.bias", d, d, da1)
+        _skinny_bwd(model, tr, linear_2, dtemb, a1, da1)
         dh1 = torch.empty(B, d, dtype=BF16, device=dev)
         ops.ew(h1, da1, dh1, 1)
-        _skinny_bwd(model, tr, dh1, x, f"time_text_embed.{name}.linear_1.weight",
-                    f"time_text_embed.{name}.linear_1.bias", d, K, None)
-    if model.lora is not None:
-        if model.lora_param.grad is None:
-            model.lora_param.grad = model.lora.ensure_grad()
-    elif model.flat_param.grad is None:
-        model.flat_param.grad = g32
+        _skinny_bwd(model, tr, linear_1, dh1, x, None)
+    if model.trainable_param.grad is None:
+        model.trainable_param.grad = model.trainable_store.ensure_grad()

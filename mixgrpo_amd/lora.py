@@ -97,9 +97,6 @@ class LoraStore:
                 off += (self.rank * width + self.ALIGN - 1) // self.ALIGN * self.ALIGN
         self.numel = off
         self.g32 = None
-        self._members = {}
-        self._order = [n for n, _ in self.layout]
-        self._shape = dict(self.layout)
         if allocate:
             self.w32 = torch.zeros(off, dtype=F32, device=self.device)
             self.w16 = torch.zeros(off, dtype=BF16, device=self.device)
@@ -145,24 +142,9 @@ class LoraStore:
             self.view(self.w32, f"{module}.lora_A").uniform_(-bound, bound, generator=g)
         self.sync_bf16()
 
-    def members(self, wname, rows_total=None):
-        """The targets among the weight rows a `_wgrad` call covers: [(module, first output column, N)].  `rows_total`: the
-        call spans that many rows of adjacent tensors starting at `wname` (a fused projection); None: `wname` alone."""
-        key = (wname, rows_total)
-        hit = self._members.get(key)
-        if hit is None:
-            hit, i, col = [], self._order.index(wname), 0
-            total = self._shape[wname][0] if rows_total is None else rows_total
-            while col < total:
-                name = self._order[i]
-                module = name[:-len(".weight")]
-                if module in self.by_module:
-                    hit.append((module, col, self._shape[name][0]))
-                col += self._shape[name][0]
-                i += 1
-            assert col == total, (wname, rows_total)
-            self._members[key] = hit
-        return hit
+    def members(self, lin):
+        """The targets among the members of the `arch.Linear` a `_wgrad` call covers: [(module, first output column, N)]."""
+        return [mem for mem in lin.members if mem[0] in self.by_module]
 
     def merge(self, store):
         """store.w16[target] = bf16(store.w32[target] + s Bt^T A) for every target (from the fp32 masters, summed in fp64, one rounding)."""

@@ -91,6 +91,26 @@ def oracle_flux(cfg, P, device=None):
     return OracleFlux()
 
 
+def small_cfg(layers=1, singles=1):
+    return dict(num_layers=layers, num_single_layers=singles, attention_head_dim=128, num_attention_heads=4,
+                joint_attention_dim=64, pooled_projection_dim=32)
+
+
+def make_inputs(B, hgrid, wgrid, L, seed=0):
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    N = hgrid * wgrid
+    x = torch.randn(B, N, 64, generator=g)
+    ehs = torch.randn(B, L, 64, generator=g).bfloat16()
+    pooled = torch.randn(B, 32, generator=g).bfloat16()
+    ids = torch.zeros(hgrid, wgrid, 3)
+    ids[..., 1] += torch.arange(hgrid)[:, None]
+    ids[..., 2] += torch.arange(wgrid)[None]
+    ids = ids.reshape(N, 3)
+    t = torch.tensor([0.954, 0.5, 0.123][:B] if B <= 3 else [0.954] * B)
+    return x, ehs, pooled, ids, torch.zeros(L, 3), t, torch.tensor([3.5]).bfloat16()
+
+
 def free_port():
     """A TCP port the kernel just handed out (bind to port 0): distinct per call, whatever the pytest pid is."""
     import socket

@@ -79,13 +79,16 @@ def test_store_layout_keys_and_shapes():
 
 
 def test_members_of_fused_projections():
+    from mixgrpo_amd.arch import describe
+    arch = describe(CFG)
     lo = LR.LoraStore(CFG, "cpu", 16, 16, "to_q,to_v,proj_mlp,add_k_proj", allocate=False)
     p, s = "transformer_blocks.0.attn", "single_transformer_blocks.1"
-    assert lo.members(f"{p}.to_q.weight", 3 * D) == [(f"{p}.to_q", 0, D), (f"{p}.to_v", 2 * D, D)]
-    assert lo.members(f"{p}.add_q_proj.weight", 3 * D) == [(f"{p}.add_k_proj", D, D)]
-    assert lo.members(f"{s}.attn.to_q.weight", 7 * D) == [(f"{s}.attn.to_q", 0, D), (f"{s}.attn.to_v", 2 * D, D),
-                                                          (f"{s}.proj_mlp", 3 * D, 4 * D)]
-    assert lo.members(f"{p}.to_out.0.weight") == [] and lo.members("proj_out.weight") == []
+    txt, img = arch.double[0].streams
+    assert lo.members(img.qkv) == [(f"{p}.to_q", 0, D), (f"{p}.to_v", 2 * D, D)]
+    assert lo.members(txt.qkv) == [(f"{p}.add_k_proj", D, D)]
+    assert lo.members(arch.single[1].qkv_mlp) == [(f"{s}.attn.to_q", 0, D), (f"{s}.attn.to_v", 2 * D, D),
+                                                  (f"{s}.proj_mlp", 3 * D, 4 * D)]
+    assert lo.members(img.out) == [] and lo.members(arch.proj_out) == []
 
 
 def test_lora_config_round_trip(tmp_path):
