@@ -437,6 +437,25 @@ int mgx_nhwc_to_image(const uint16_t* x, long ld, uint16_t* img, int Cout, int H
 /* P[r, :n] = bf16(softmax(scale * S[r, :n])), S fp32 (the mid block's single-head attention over H W <= 16384 tokens) */
 int mgx_softmax_rows_f32(const float* S, long lds, uint16_t* P, long ldp, int M, int n, float scale, void* stream);
 
+/* ---- VAE encode: the encoder half of the same AutoencoderKL (`vae.encode(x).latent_dist`), on the kernels above plus these.
+ * The encoder's downsampler, diffusers' Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)) then Conv2d(3, stride=2) -- semantics
+ * recollected, PARITY UNPINNED (diffusers is not vendored by the reference; its fastvideo/models/hunyuan/vae/
+ * unet_causal_3d_blocks.py:208 DownsampleCausal3D witnesses the structure only, its padding differs).
+ * x: padded NHWC image of an H x W activation, H and W even, C in {64, 128, 256, 512}; out plain [(H/2)(W/2)][ld_out]:
+ * out(y, x) = bias + sum_{ky,kx} w[ky][kx] . in(2y + ky, 2x + kx), `in` zero outside the activation (the bottom / right border of
+ * x; its top / left border is never read).  Wt, bias, Cout, alignments as for mgx_conv3x3_nhwc; no residual form. */
+int mgx_conv3x3s2_nhwc(const uint16_t* x, const uint16_t* Wt, const uint16_t* bias, uint16_t* out, long ld_out, int H, int W,
+                       int C, int Cout, void* stream);
+/* first C channels of a plain [H W][ld] image -> interior of a padded [(H + 2)(W + 2)][C] image (`out` at pixel (1, 1)); 16-byte
+ * copies: C % 8 == 0, ld % 8 == 0.  The downsampler's input: a ResnetBlock's output (unet_causal_3d_blocks.py:404-462) is plain. */
+int mgx_pad_nhwc(const uint16_t* x, long ld, uint16_t* out, int H, int W, int C, void* stream);
+/* DiagonalGaussianDistribution (fastvideo/models/hunyuan/vae/vae.py:321-353, .mode() :384) as torch evaluates it on bf16 tensors,
+ * every op rounding to bf16: moments plain NHWC [H W][ld], channels [0, Cz) the mean, [Cz, 2 Cz) the logvar (chunk, :331) ->
+ * [Cz][H][W] bf16 each: mean; std = bf16(exp(bf16(0.5 * clamp(logvar, -30, 20)))) (:332,334);
+ * sample = bf16(mean + bf16(std * noise)) (:352), noise [Cz][H][W] bf16; noise == NULL: sample = mean (.mode()). */
+int mgx_diag_gaussian_nhwc(const uint16_t* moments, long ld, const uint16_t* noise, uint16_t* mean, uint16_t* std,
+                           uint16_t* sample, int Cz, int H, int W, void* stream);
+
 /* ---- low-rank adapters (csrc/lora.hip).  A target Linear y = x (W0 + s B A)^T + b with A [r, K], B [N, r]; B is held
  * transposed (Bt [r, N]) so that both adapter halves are "r rows x wide" and each kernel serves both.  r in {16, 32, 64, 128},
  * Kin % 64 == 0, any M >= 1; everything else is refused.  No atomics: every result is bit-reproducible.

@@ -96,6 +96,9 @@ SIGNATURES = {
     "mgx_latents_to_pad_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "mgx_nhwc_to_image": (_I, [_P, _L, _P, _I, _I, _I, _P]),
     "mgx_softmax_rows_f32": (_I, [_P, _L, _P, _L, _I, _I, _F, _P]),
+    "mgx_conv3x3s2_nhwc": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
+    "mgx_pad_nhwc": (_I, [_P, _L, _P, _I, _I, _I, _P]),
+    "mgx_diag_gaussian_nhwc": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _P]),
     "mgx_skinny_dgrad": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _P]),
     "mgx_ew_bf16": (_I, [_P, _P, _P, _L, _I, _P]),
     "mgx_sincos_embed": (_I, [_P, _P, _I, _P]),

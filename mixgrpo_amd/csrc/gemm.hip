@@ -1425,6 +1425,29 @@ extern "C" int mgx_conv3x3_nhwc(const uint16_t* x, const uint16_t* Wt, const uin
   return residual ? launch<EPI_BIAS_GATE_RES, true>(g, st) : launch<EPI_BIAS, true>(g, st);
 }
 
+// 3x3 convolution, stride 2, over F.pad(x, (0, 1, 0, 1)) -- the encoder's downsampler -- on the same kernels, unchanged: the
+// GEMM's A rows follow a RowMap, so output pixel (y, x) starts at padded pixel (1 + 2y, 1 + 2x): the base pointer at padded
+// pixel (1, 1), 2 C elements between consecutive rows, W / 2 rows per image row, two padded image rows between batches.  The
+// taps step through the image as for stride 1 (conv_dy, conv_dx).  The last padded pixel read is (H + 1, W + 1): the bottom
+// and right zero border is the padding, the top and left border is never read.  x padded [(H + 2)(W + 2)][C], H and W even;
+// out plain [(H / 2)(W / 2)][ld_out].
+extern "C" int mgx_conv3x3s2_nhwc(const uint16_t* x, const uint16_t* Wt, const uint16_t* bias, uint16_t* out, long ld_out, int H,
+                                  int Wd, int C, int Cout, void* stream) {
+  MGX_REQUIRE(x && Wt && out && H > 0 && Wd > 0, "bad argument");
+  MGX_REQUIRE(H % 2 == 0 && Wd % 2 == 0, "a stride-2 convolution takes even image sides");
+  MGX_REQUIRE(C == 64 || C == 128 || C == 256 || C == 512, "channels per tap must be 64, 128, 256 or 512 (pad with zeros)");
+  MGX_REQUIRE(Cout > 0 && Cout % 4 == 0 && ld_out >= Cout && ld_out % 4 == 0, "output channels must be a multiple of 4");
+  MGX_REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)Wt % 16 == 0) && ((uintptr_t)out % 8 == 0), "operands must be 16-byte aligned");
+  const long Wp = Wd + 2;
+  MGX_REQUIRE((long)(H + 2) * Wp * C * 2 < (1L << 32) && (long)Cout * 9 * C * 2 < (1L << 32), "image too large for one call");
+  GemmArgs g = gemm_args(x + (Wp + 1) * C, Wt, bias, out, (H / 2) * (Wd / 2), Cout, 9 * C, RowMap{2L * C, Wd / 2, 2 * Wp * C},
+                         RowMap{ld_out, 1L << 30, 0}, 9L * C);
+  g.conv_shift = C == 64 ? 0 : (C == 128 ? 1 : (C == 256 ? 2 : 3));
+  g.conv_dy = Wp * C; g.conv_dx = C;
+  g.span32 = 1;                           // (the image-size check above bounds every offset from the shifted base as well)
+  return launch<EPI_BIAS, true>(g, (hipStream_t)stream);
+}
+
 extern "C" long mgx_transpose_partial_elems(int M, int N) { return (long)cdiv(M, 64) * N; }   // covers both paths
 
 extern "C" int mgx_transpose_bf16(const uint16_t* in, uint16_t* out, float* colsum_partial, float* colsum_out,

@@ -6,6 +6,8 @@
 // What it replaces: `vae.decode(latents)` of fastvideo/train_grpo_flux.py:279-289 (bf16 weights under bf16 autocast):
 // GroupNorm(32 groups, eps 1e-6) runs in fp32 on the bf16 tensor and its fp32 result goes through SiLU in fp32 before the
 // next convolution's input cast to bf16 -- one rounding, here at the store; nearest-neighbour upsampling is exact.
+// The encoder half (`vae.encode`) adds the plain-to-padded copy in front of its stride-2 downsampler (mgx_conv3x3s2_nhwc) and
+// the DiagonalGaussianDistribution of fastvideo/models/hunyuan/vae/vae.py:321-353,384 behind conv_out.
 #include "common.h"
 
 namespace {
@@ -136,6 +138,40 @@ __global__ void __launch_bounds__(256) upsample2x_pad_kernel(const bf16_raw* __r
   }
 }
 
+// plain [H W][ld] (first C channels) -> interior of a padded [(H + 2)(W + 2)][C] image (out points at pixel (1, 1))
+__global__ void __launch_bounds__(256) pad_kernel(const bf16_raw* __restrict__ x, long ld, bf16_raw* __restrict__ out, int H,
+                                                  int Wd, int C) {
+  const int tpr = C / 8;
+  const long total = (long)H * Wd * tpr;
+  const long orow = (long)(Wd + 2) * C;
+  for (long id = (long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long)gridDim.x * 256) {
+    const long p = id / tpr;
+    const int c0 = (int)(id - p * tpr) * 8;
+    const long yy = p / Wd, xx = p - yy * Wd;
+    *reinterpret_cast<uint4*>(out + yy * orow + xx * C + c0) = *reinterpret_cast<const uint4*>(x + p * ld + c0);
+  }
+}
+
+// DiagonalGaussianDistribution on bf16 tensors: every torch op rounds its result to bf16.  moments plain [HW][ld]: channels
+// [0, Cz) the mean, [Cz, 2 Cz) the logvar -> mean, std, sample [Cz][HW]
+__global__ void __launch_bounds__(256) diag_gaussian_kernel(const bf16_raw* __restrict__ mom, long ld,
+                                                            const bf16_raw* __restrict__ noise, bf16_raw* __restrict__ mean,
+                                                            bf16_raw* __restrict__ stdv, bf16_raw* __restrict__ sample, int Cz,
+                                                            long HW) {
+  const long total = HW * Cz;
+  for (long id = (long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long)gridDim.x * 256) {
+    const int c = (int)(id / HW);
+    const long p = id - (long)c * HW;
+    const bf16_raw m = mom[p * ld + c];
+    float lv = bf2f(mom[p * ld + Cz + c]);
+    lv = lv < -30.0f ? -30.0f : (lv > 20.0f ? 20.0f : lv);                        // torch.clamp: exact in bf16, NaN stays NaN
+    const bf16_raw s = f2bf(expf(bf2f(f2bf(0.5f * lv))));
+    mean[id] = m;
+    stdv[id] = s;
+    sample[id] = noise ? f2bf(bf2f(m) + bf2f(f2bf(bf2f(s) * bf2f(noise[id])))) : m;
+  }
+}
+
 // latents [Cin][H][W] fp32 -> bf16 interior of a padded NHWC image with C channels (channels >= Cin stay zero)
 __global__ void __launch_bounds__(256) nchw_to_pad_kernel(const float* __restrict__ z, bf16_raw* __restrict__ out, int Cin, int H,
                                                           int Wd, int C) {
@@ -231,6 +267,26 @@ extern "C" int mgx_upsample2x_pad_nhwc(const uint16_t* x, uint16_t* out, int H, 
   const long total = (long)4 * H * Wd * (C / 8);
   const int grid = (int)((total + 255) / 256 < 256L * 16 ? (total + 255) / 256 : 256L * 16);
   upsample2x_pad_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, out, H, Wd, C);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int mgx_pad_nhwc(const uint16_t* x, long ld, uint16_t* out, int H, int Wd, int C, void* stream) {
+  MGX_REQUIRE(x && out && H > 0 && Wd > 0 && C > 0 && C % 8 == 0 && ld >= C && ld % 8 == 0, "bad argument");
+  MGX_REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0), "16-byte aligned images");
+  const long total = (long)H * Wd * (C / 8);
+  const int grid = (int)((total + 255) / 256 < 256L * 16 ? (total + 255) / 256 : 256L * 16);
+  pad_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, ld, out, H, Wd, C);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int mgx_diag_gaussian_nhwc(const uint16_t* moments, long ld, const uint16_t* noise, uint16_t* mean, uint16_t* std,
+                                      uint16_t* sample, int Cz, int H, int Wd, void* stream) {
+  MGX_REQUIRE(moments && mean && std && sample && Cz > 0 && ld >= 2L * Cz && H > 0 && Wd > 0, "bad argument");
+  const long total = (long)H * Wd * Cz;
+  const int grid = (int)((total + 255) / 256 < 256L * 16 ? (total + 255) / 256 : 256L * 16);
+  diag_gaussian_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(moments, ld, noise, mean, std, sample, Cz, (long)H * Wd);
   MGX_CHECK_LAUNCH();
   return MGX_OK;
 }

@@ -419,5 +419,22 @@ def nhwc_to_image(x, ld, img, Cout, H, W):
     check(lib().mgx_nhwc_to_image(ptr(x), ld, ptr(img), Cout, H, W, stream()))
 
 
+def conv3x3s2(xpad, Wt, bias, out, H, W, C, Cout, ld_out=None):
+    """out[(H/2)(W/2), Cout] = conv3x3(F.pad(x, (0, 1, 0, 1)), stride 2) + bias: xpad the zero-bordered NHWC image
+    [(H+2), (W+2), C] of the H x W activation x (H, W even), Wt [Cout, 3, 3, C]."""
+    check(lib().mgx_conv3x3s2_nhwc(ptr(xpad), ptr(Wt), ptr(bias), ptr(out), Cout if ld_out is None else ld_out, H, W, C, Cout,
+                                   stream()))
+
+
+def pad_nhwc(x, ld, outpad, H, W, C):
+    """first C channels of plain [H W, ld] -> interior of the zero-bordered [(H+2), (W+2), C] image `outpad`"""
+    check(lib().mgx_pad_nhwc(ptr(x), ld, outpad.view(-1)[(W + 2) * C + C:].data_ptr(), H, W, C, stream()))
+
+
+def diag_gaussian(moments, ld, noise, mean, std, sample, Cz, H, W):
+    """moments plain NHWC [H W, ld] (mean | logvar) -> mean, std, sample [Cz, H, W] bf16; noise None: sample = mean"""
+    check(lib().mgx_diag_gaussian_nhwc(ptr(moments), ld, ptr(noise), ptr(mean), ptr(std), ptr(sample), Cz, H, W, stream()))
+
+
 def softmax_rows(S, P, M, n, scale):
     check(lib().mgx_softmax_rows_f32(ptr(S), S.stride(0), ptr(P), P.stride(0), M, n, scale, stream()))

@@ -42,6 +42,20 @@ def flow_match_sigmas(num_inference_steps, mu, sigmas=None):
     return torch.cat([shifted, torch.zeros(1)]), shifted * 1000.0
 
 
+def img2img_start(num_inference_steps, strength):
+    """Index of the first step an image-to-image run takes in the full schedule of `num_inference_steps`: the last
+    `int(num_inference_steps * strength)` steps are run (strength 1.0: all of them, from pure noise).  diffusers' img2img
+    `get_timesteps`, recollected -- PARITY UNPINNED (diffusers is absent offline).  `strength` outside (0, 1], or one that leaves
+    no step, is an error."""
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength must be in (0, 1], not {strength}")
+    init = min(int(num_inference_steps * strength), num_inference_steps)
+    t_start = int(max(num_inference_steps - init, 0))
+    if num_inference_steps - t_start < 1:
+        raise ValueError(f"strength {strength} leaves none of the {num_inference_steps} steps to run")
+    return t_start
+
+
 class DualFluxSampler:
     """`transformer`: base model, `transformer_new`: tuned model (both mixgrpo_amd.flux.FluxTransformer2DModel)."""
 
@@ -69,9 +83,16 @@ class DualFluxSampler:
     def __call__(self, prompt_embeds, pooled_prompt_embeds, height=1024, width=1024, num_inference_steps=28,
                  mix_sampling_steps=10, sigmas=None, guidance_scale=3.5, generator=None, latents=None,
                  true_cfg_scale=1.0, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None,
-                 text_ids=None, max_sequence_length=512, output_type="latent"):
+                 text_ids=None, max_sequence_length=512, output_type="latent", image=None, strength=1.0):
         """`output_type`: "latent" (packed latents, the default here) | "pt" ([B, 3, H, W] in [0, 1]) | "np" ([B, H, W, 3] float32)
-        | "pil" -- the reference's tail (:387-393): unpack, `/ scaling_factor + shift_factor`, `vae.decode`, postprocess."""
+        | "pil" -- the reference's tail (:387-393): unpack, `/ scaling_factor + shift_factor`, `vae.decode`, postprocess.
+
+        `image` ([B, 3, height, width] in [-1, 1]): image-to-image, diffusers' FluxImg2ImgPipeline -- recollected, PARITY UNPINNED
+        (diffusers is absent offline; the reference has no such pipeline).  The run takes the steps `img2img_start(...)..` of the
+        full schedule and starts from `sigma * noise + (1 - sigma) * encode_image(image)` at that step's sigma
+        (FlowMatchEulerDiscreteScheduler.scale_noise, evaluated in the latents' dtype); `mix_sampling_steps` keeps counting in
+        the full schedule.  The generator gives the posterior's noise first, then the initial noise.  `latents` cannot be given
+        as well.  With `image=None` nothing changes."""
         dev = self.transformer.store.device
         if output_type != "latent" and self.vae is None:
             raise ValueError(f'output_type="{output_type}" needs a VAE: DualFluxSampler(..., vae=AutoencoderKL.from_pretrained(...))')
@@ -83,6 +104,17 @@ class DualFluxSampler:
         dtype = prompt_embeds.dtype
         hl, wl = 2 * (int(height) // 16), 2 * (int(width) // 16)        # latent grid (VAE factor 8, even)
         C = self.transformer.cfg.in_channels // 4
+        t_start = 0
+        image_latents = None
+        if image is not None:
+            if self.vae is None or not getattr(self.vae, "has_encoder", False):
+                raise ValueError("image= needs a VAE with an encoder: DualFluxSampler(..., vae=AutoencoderKL.from_pretrained(...))")
+            if latents is not None:
+                raise ValueError("image= draws its own initial noise: do not pass latents as well")
+            if tuple(image.shape[-2:]) != (int(height), int(width)):
+                raise ValueError(f"image is {tuple(image.shape[-2:])}, height x width {int(height)} x {int(width)}")
+            t_start = img2img_start(num_inference_steps if sigmas is None else len(sigmas), strength)
+            image_latents = self.encode_image(image, generator).to(dtype)
         if latents is None:
             z = torch.randn(B, C, hl, wl, generator=generator, device=dev if generator is None else generator.device,
                             dtype=dtype).to(dev)
@@ -96,7 +128,10 @@ class DualFluxSampler:
         if self.transformer.cfg.guidance_embeds:
             guidance = torch.full([1], guidance_scale, device=dev, dtype=torch.float32).expand(B)
         do_true_cfg = true_cfg_scale > 1 and negative_prompt_embeds is not None and negative_pooled_prompt_embeds is not None
-        for i in range(len(timesteps)):
+        if image_latents is not None:
+            s0 = sig[t_start].to(device=dev, dtype=latents.dtype)
+            latents = s0 * latents + (1.0 - s0) * image_latents
+        for i in range(t_start, len(timesteps)):
             t = timesteps[i].to(dev).expand(B).to(latents.dtype)
             model = self.transformer_new if i < mix_sampling_steps else self.transformer
             kw = dict(hidden_states=latents, timestep=t / 1000, guidance=guidance, txt_ids=text_ids, img_ids=img_ids,
@@ -112,6 +147,23 @@ class DualFluxSampler:
         if output_type == "latent":
             return latents
         return self.decode_latents(latents, height, width, output_type)
+
+    @torch.no_grad()
+    def encode_image(self, image, generator=None, sample_mode="sample"):
+        """image [B, 3, H, W] in [-1, 1] -> packed, normalised latents `(z - shift_factor) * scaling_factor`, [B, (H/16)(W/16), 64]
+        bf16, z a sample ("sample") or the mode ("argmax") of `vae.encode(image).latent_dist` -- the inverse of the tail in
+        `decode_latents` (diffusers' `_encode_vae_image` + `_pack_latents`, recollected)."""
+        from .latents import pack_latents
+        if self.vae is None or not getattr(self.vae, "has_encoder", False):
+            raise ValueError("encode_image needs a VAE with an encoder")
+        if sample_mode not in ("sample", "argmax"):
+            raise ValueError(f"unknown sample_mode {sample_mode}")
+        cfg = self.vae.config
+        dist = self.vae.encode(image, return_dict=False)[0]
+        z = dist.sample(generator) if sample_mode == "sample" else dist.mode()
+        z = (z - cfg.shift_factor) * cfg.scaling_factor
+        B, C, h, w = z.shape
+        return pack_latents(z, B, C, h, w)
 
     def decode_latents(self, latents, height, width, output_type="pt"):
         """Reference :390-393 with diffusers' VaeImageProcessor.postprocess restated for its three plain outputs:

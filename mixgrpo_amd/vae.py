@@ -1,8 +1,13 @@
-"""FLUX VAE decode on the HIP kernels: the `vae` object of the reference's rollout,
+"""FLUX VAE on the HIP kernels: the `vae` object of the reference's rollout,
     vae = AutoencoderKL.from_pretrained(path, subfolder="vae", torch_dtype=torch.bfloat16)       (train_grpo_flux.py:697-701)
     vae.enable_tiling(); image = vae.decode(latents, return_dict=False)[0]                        (:279-289)
--- diffusers' AutoencoderKL, decoder half only (the trainer never encodes).  Same constructor call, `.config`, `.enable_tiling()`,
-`.decode(z, return_dict=False)`; weights from the published `vae/diffusion_pytorch_model.safetensors` (diffusers key names).
+-- diffusers' AutoencoderKL.  Same constructor call, `.config`, `.enable_tiling()`, `.decode(z, return_dict=False)`; weights from
+the published `vae/diffusion_pytorch_model.safetensors` (diffusers key names).  The trainer never encodes; the encoder half
+(`.encode(x).latent_dist.sample()`, `.tiled_encode`) is here for image-to-image sampling, latent datasets and the
+`encode(decode(z))` self-check of a set of weights: the same kernels in the opposite order, with a stride-2 convolution
+(Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)) + Conv2d(3, stride=2) -- recollected from diffusers, parity unpinned) in place of
+the upsampler and the DiagonalGaussianDistribution of fastvideo/models/hunyuan/vae/vae.py:321-353 behind conv_out.  Encode tiling
+follows `spatial_tiled_encode` (autoencoder_kl_causal_3d.py:408-470): the MOMENTS of the tiles are blended, then one Gaussian.
 
 Layout: one image at a time, activations NHWC bf16; every 3x3 convolution is an implicit GEMM on the MFMA GEMM kernels over a
 zero-bordered copy written by the GroupNorm + SiLU (or upsample) pass in front of it, residual sums ride the GEMM epilogue, the
@@ -33,6 +38,9 @@ class VaeConfig:
     scaling_factor: float = 0.3611
     shift_factor: float = 0.1159
     mid_block_add_attention: bool = True
+    in_channels: int = 3                 # the encoder's three: other values are refused at `encode`
+    use_quant_conv: bool = False         # (FLUX's VAE has no quant conv)
+    double_z: bool = True
 
 
 def _pad_ch(c):
@@ -55,6 +63,7 @@ class AutoencoderKL:
             if ch not in (64, 128, 256, 512):
                 raise ValueError("block_out_channels must be 64, 128, 256 or 512 (channels per convolution tap)")
         self.P = None
+        self.has_encoder = False
         self._buf = {}
         self._ones = torch.ones(512, dtype=BF16, device=self.device)
 
@@ -83,16 +92,27 @@ class AutoencoderKL:
         return self
 
     def load_state_dict(self, sd):
-        """diffusers keys (`decoder.*`; encoder / quant-conv entries are ignored).  Conv weights OIHW -> [O][kh][kw][I] bf16 with
-        the input channels padded to the kernel's tap width and conv_out's 3 output channels to 4."""
+        """diffusers keys.  `decoder.*` is required; `encoder.*` is loaded if and only if EVERY encoder tensor is there (a state
+        dict with none or only some of them gives a decoder-only object: `has_encoder` False); quant-conv entries are ignored.
+        Conv weights OIHW -> [O][kh][kw][I] bf16 with the input channels padded to the kernel's tap width and the output
+        channels to a multiple of 4."""
         c = self.config
-        dev = self.device
-        P = {}
-        need = [k for k in _decoder_keys(c)]
+        need = _decoder_keys(c)
         missing = [k for k in need if k not in sd]
         if missing:
             raise KeyError(f"VAE state dict lacks {len(missing)} decoder tensors, e.g. {missing[:3]}")
-        for k in need:
+        P = {}
+        self._convert(sd, need, "decoder", P)
+        enc = _encoder_keys(c)
+        self.has_encoder = all(k in sd for k in enc)
+        if self.has_encoder:
+            self._convert(sd, enc, "encoder", P)
+        self.P = P
+        return self
+
+    def _convert(self, sd, keys, half, P):
+        c, dev = self.config, self.device
+        for k in keys:
             t = sd[k].to(dev)
             if t.dim() == 4 and t.shape[-1] == 3:
                 O, I = t.shape[0], t.shape[1]
@@ -108,25 +128,25 @@ class AutoencoderKL:
                 P[k] = b
             else:
                 P[k] = t.to(BF16).contiguous()
-        a = "decoder.mid_block.attentions.0"
+        a = half + ".mid_block.attentions.0"
         if c.mid_block_add_attention:
             P[a + ".qkv.weight"] = torch.cat([P[f"{a}.to_{n}.weight"] for n in "qkv"], 0).contiguous()
             P[a + ".qkv.bias"] = torch.cat([P[f"{a}.to_{n}.bias"] for n in "qkv"], 0).contiguous()
-        self.P = P
-        return self
 
     def init_synthetic(self, seed=0):
-        """Random bf16 weights of the configured architecture (no checkpoint offline); same generator as oracle/vae.py."""
-        g = torch.Generator().manual_seed(seed)
+        """Random bf16 weights of the configured architecture (no checkpoint offline); the decoder's from the same generator as
+        oracle/vae.py, the encoder's from a second one (seed + 1) drawn after them, so the decoder's do not depend on it."""
         sd = {}
-        for k, shp in _decoder_shapes(self.config).items():
-            if k.endswith(".weight") and len(shp) == 1:
-                sd[k] = (1.0 + 0.1 * torch.randn(shp, generator=g)).to(BF16)
-            elif k.endswith(".bias"):
-                sd[k] = (0.05 * torch.randn(shp, generator=g)).to(BF16)
-            else:
-                fan_in = shp[1] * (shp[2] * shp[3] if len(shp) == 4 else 1)
-                sd[k] = (torch.randn(shp, generator=g) / fan_in ** 0.5).to(BF16)
+        for shapes, half_seed in ((_decoder_shapes(self.config), seed), (_encoder_shapes(self.config), seed + 1)):
+            g = torch.Generator().manual_seed(half_seed)
+            for k, shp in shapes.items():
+                if k.endswith(".weight") and len(shp) == 1:
+                    sd[k] = (1.0 + 0.1 * torch.randn(shp, generator=g)).to(BF16)
+                elif k.endswith(".bias"):
+                    sd[k] = (0.05 * torch.randn(shp, generator=g)).to(BF16)
+                else:
+                    fan_in = shp[1] * (shp[2] * shp[3] if len(shp) == 4 else 1)
+                    sd[k] = (torch.randn(shp, generator=g) / fan_in ** 0.5).to(BF16)
         return self.load_state_dict(sd)
 
     # ---------------------------------------------------------------------------------------------- buffers
@@ -232,6 +252,47 @@ class AutoencoderKL:
         ops.nhwc_to_image(y, 8, img, c.out_channels, H, W)
         return img
 
+    def _encoder(self, x):
+        """x [in_channels, H, W] fp32 on the device -> the moments, plain NHWC bf16 [(H / f)(W / f)][2 latent_channels] with
+        f = 2^(len(block_out_channels) - 1): channels [0, latent_channels) the mean, the rest the logvar."""
+        c, P = self.config, self.P
+        ch = list(c.block_out_channels)
+        f = 2 ** (len(ch) - 1)
+        _, H, W = x.shape
+        if H % f or W % f or H <= 0 or W <= 0:
+            raise ValueError(f"the encoder takes image sides that are multiples of {f}, not {H} x {W}")
+        Ci = _pad_ch(c.in_channels)
+        # its own buffer, like the decoder's pad_z: only the first `in_channels` of its Ci channels are ever written
+        pad = self._padded(H, W, Ci, tag="pad_x")
+        ops.latents_to_pad(x.contiguous(), pad, c.in_channels, H, W, Ci)
+        y = self._plain("x", H * W, ch[0])
+        ops.conv3x3(pad, P["encoder.conv_in.weight"], P["encoder.conv_in.bias"], y, H, W, Ci, ch[0])
+        x = y
+        prev = ch[0]
+        for i, co in enumerate(ch):
+            for j in range(c.layers_per_block):
+                x = self._resnet(f"encoder.down_blocks.{i}.resnets.{j}", x, H, W, prev if j == 0 else co, co)
+            if i != len(ch) - 1:                                 # Downsample2D(padding=0): pad right / bottom, 3x3 stride 2
+                pad = self._padded(H, W, co)
+                ops.pad_nhwc(x, co, pad, H, W, co)
+                k = f"encoder.down_blocks.{i}.downsamplers.0.conv"
+                y = self._plain("x", (H // 2) * (W // 2), co)
+                ops.conv3x3s2(pad, P[k + ".weight"], P[k + ".bias"], y, H, W, co, co)
+                H, W = H // 2, W // 2
+                x = y
+            prev = co
+        x = self._resnet("encoder.mid_block.resnets.0", x, H, W, prev, prev)
+        if c.mid_block_add_attention:
+            x = self._attention("encoder.mid_block.attentions.0", x, H, W, prev)
+        x = self._resnet("encoder.mid_block.resnets.1", x, H, W, prev, prev)
+        pad = self._padded(H, W, prev)
+        ops.group_norm(x, P["encoder.conv_norm_out.weight"], P["encoder.conv_norm_out.bias"], pad, H, W, prev,
+                       c.norm_num_groups, True, True)
+        Cm = 2 * c.latent_channels
+        mom = torch.empty(H * W, Cm, dtype=BF16, device=self.device)      # (not a shared buffer: tiled_encode keeps several)
+        ops.conv3x3(pad, P["encoder.conv_out.weight"], P["encoder.conv_out.bias"], mom, H, W, prev, Cm)
+        return mom
+
     # ---------------------------------------------------------------------------------------------- public surface
     def enable_tiling(self, use_tiling=True):
         self.use_tiling = use_tiling
@@ -275,6 +336,104 @@ class AutoencoderKL:
         else:
             img = self._decode_batch(z)
         return {"sample": img} if return_dict else (img,)
+
+    def _encode_batch(self, x):
+        """x [B, 3, H, W] -> moments NHWC [B, H / f, W / f, 2 latent_channels] bf16"""
+        f = 2 ** (len(self.config.block_out_channels) - 1)
+        return torch.stack([self._encoder(x[b].float()).view(x.shape[-2] // f, x.shape[-1] // f, -1) for b in range(x.shape[0])])
+
+    def _tiled_moments(self, x):
+        """autoencoder_kl_causal_3d.py:408-462 in 2-D, on NHWC moments (rows are dim 1, columns dim 2): image tiles of
+        `tile_sample_min_size`, their moments blended in place on the later tile and cropped as in `tiled_decode`."""
+        tl, ts, ov = self.tile_latent_min_size, self.tile_sample_min_size, self.tile_overlap_factor
+        overlap_size = int(ts * (1 - ov))
+        blend_extent = int(tl * ov)
+        row_limit = tl - blend_extent
+        rows = []
+        for i in range(0, x.shape[-2], overlap_size):
+            rows.append([self._encode_batch(x[:, :, i:i + ts, j:j + ts]) for j in range(0, x.shape[-1], overlap_size)])
+        result_rows = []
+        for i, row in enumerate(rows):
+            result_row = []
+            for j, tile in enumerate(row):
+                if i > 0:
+                    tile = _blend(rows[i - 1][j], tile, blend_extent, 1)
+                if j > 0:
+                    tile = _blend(row[j - 1], tile, blend_extent, 2)
+                result_row.append(tile[:, :row_limit, :row_limit])
+            result_rows.append(torch.cat(result_row, dim=2))
+        return torch.cat(result_rows, dim=1)
+
+    def _check_encode(self):
+        c = self.config
+        if c.in_channels != 3 or c.use_quant_conv or not c.double_z or c.latent_channels % 2:
+            raise ValueError("encode handles in_channels = 3, use_quant_conv = False, double_z = True and an even number of "
+                             "latent channels (the FLUX VAE)")
+        if self.P is None:
+            raise RuntimeError("VAE weights not loaded")
+        if not self.has_encoder:
+            raise RuntimeError("this VAE is decoder-only: its state dict did not hold every encoder.* tensor, so it has no encoder")
+
+    @torch.no_grad()
+    def tiled_encode(self, x, return_dict=True, return_moments=False):
+        """`spatial_tiled_encode` (autoencoder_kl_causal_3d.py:408-470): one Gaussian over the blended moments (:466), or --
+        `return_moments` (:463-464) -- the moments themselves, [B, 2 latent_channels, h, w]."""
+        self._check_encode()
+        mom = self._tiled_moments(x.to(self.device))
+        if return_moments:
+            return mom.permute(0, 3, 1, 2)
+        dist = DiagonalGaussianDistribution(mom, self.config.latent_channels)
+        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+
+    @torch.no_grad()
+    def encode(self, x, return_dict=True):
+        """x [B, 3, H, W] in [-1, 1] -> `.latent_dist`, the posterior over [B, latent_channels, H / 8, W / 8] latents (raw: the
+        caller applies `(z - shift_factor) * scaling_factor`).  Tiled only when tiling is enabled and a side exceeds the tile
+        (autoencoder_kl_causal_3d.py:307-310); a 1024^2 image is one tile."""
+        self._check_encode()
+        x = x.to(self.device)
+        ts = self.tile_sample_min_size
+        if self.use_tiling and (x.shape[-1] > ts or x.shape[-2] > ts):
+            mom = self._tiled_moments(x)
+        else:
+            mom = self._encode_batch(x)
+        dist = DiagonalGaussianDistribution(mom, self.config.latent_channels)
+        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+
+
+class AutoencoderKLOutput:
+    def __init__(self, latent_dist):
+        self.latent_dist = latent_dist
+
+
+class DiagonalGaussianDistribution:
+    """fastvideo/models/hunyuan/vae/vae.py:321-353,384 on bf16 tensors, from NHWC moments [B, h, w, 2 Cz] (csrc/vae.hip:
+    mgx_diag_gaussian_nhwc).  `.parameters`, `.mean`, `.logvar` (clamped), `.std`, `.var` are [B, Cz or 2 Cz, h, w] bf16."""
+
+    def __init__(self, moments, Cz):
+        self._moments, self._Cz = moments.contiguous(), Cz
+        self.parameters = self._moments.permute(0, 3, 1, 2)
+        self.mean, self.std, _ = self._run(None)
+        self.logvar = torch.clamp(self.parameters[:, Cz:], -30.0, 20.0)
+        self.var = torch.exp(self.logvar)
+
+    def _run(self, noise):
+        m = self._moments
+        B, h, w, ld = m.shape
+        mean, std, sample = (torch.empty(B, self._Cz, h, w, dtype=BF16, device=m.device) for _ in range(3))
+        for b in range(B):
+            ops.diag_gaussian(m[b], ld, None if noise is None else noise[b], mean[b], std[b], sample[b], self._Cz, h, w)
+        return mean, std, sample
+
+    def sample(self, generator=None):
+        """mean + std * noise, the noise drawn as bf16 on the device (on the generator's device, if one is given)."""
+        dev = self.mean.device
+        noise = torch.randn(self.mean.shape, generator=generator, device=dev if generator is None else generator.device,
+                            dtype=BF16).to(dev)
+        return self._run(noise)[2]
+
+    def mode(self):
+        return self.mean
 
 
 def _blend(a, b, blend_extent, dim):
@@ -338,3 +497,49 @@ def _decoder_shapes(cfg):
 
 def _decoder_keys(cfg):
     return list(_decoder_shapes(cfg))
+
+
+def _encoder_shapes(cfg):
+    """diffusers key -> shape for the encoder half; `i` runs in the forward order of `block_out_channels`."""
+    ch = list(cfg.block_out_channels)
+    out = {}
+
+    def conv(name, co, ci, k):
+        out[name + ".weight"] = (co, ci, k, k)
+        out[name + ".bias"] = (co,)
+
+    def norm(name, c):
+        out[name + ".weight"] = (c,)
+        out[name + ".bias"] = (c,)
+
+    def resnet(name, ci, co):
+        norm(name + ".norm1", ci)
+        conv(name + ".conv1", co, ci, 3)
+        norm(name + ".norm2", co)
+        conv(name + ".conv2", co, co, 3)
+        if ci != co:
+            conv(name + ".conv_shortcut", co, ci, 1)
+
+    conv("encoder.conv_in", ch[0], cfg.in_channels, 3)
+    prev = ch[0]
+    for i, co in enumerate(ch):
+        for j in range(cfg.layers_per_block):
+            resnet(f"encoder.down_blocks.{i}.resnets.{j}", prev if j == 0 else co, co)
+        if i != len(ch) - 1:
+            conv(f"encoder.down_blocks.{i}.downsamplers.0.conv", co, co, 3)
+        prev = co
+    resnet("encoder.mid_block.resnets.0", prev, prev)
+    if cfg.mid_block_add_attention:
+        a = "encoder.mid_block.attentions.0"
+        norm(a + ".group_norm", prev)
+        for n in ("to_q", "to_k", "to_v", "to_out.0"):
+            out[f"{a}.{n}.weight"] = (prev, prev)
+            out[f"{a}.{n}.bias"] = (prev,)
+    resnet("encoder.mid_block.resnets.1", prev, prev)
+    norm("encoder.conv_norm_out", prev)
+    conv("encoder.conv_out", (2 if cfg.double_z else 1) * cfg.latent_channels, prev, 3)
+    return out
+
+
+def _encoder_keys(cfg):
+    return list(_encoder_shapes(cfg))
