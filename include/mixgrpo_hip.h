@@ -423,7 +423,8 @@ int mgx_conv3x3_nhwc(const uint16_t* x, const uint16_t* Wt, const uint16_t* bias
                      const uint16_t* ones, int H, int W, int C, int Cout, int residual, void* stream);
 /* y = [silu](GroupNorm(x; G groups, eps, affine gamma / beta [C] bf16)) in fp32 on a plain bf16 image x [H W][ld], one rounding
  * to bf16 at the store.  Output pixel (y, x) goes to out + y * out_row + x * out_px (elements): a plain matrix or the interior of
- * a padded image.  ws: fp32 scratch of mgx_group_norm_workspace(H W, C, G) elements. */
+ * a padded image.  The group statistics (E[x^2] - mean^2) are summed in fp64 from fp32 chains of 64 rows, which are exact for
+ * bf16 data.  ws: fp32 scratch of mgx_group_norm_workspace(H W, C, G) elements, 8-byte aligned. */
 long mgx_group_norm_workspace(long M, int C, int G);
 int mgx_group_norm_nhwc(const uint16_t* x, long ld, const uint16_t* gamma, const uint16_t* beta, uint16_t* out, long out_row,
                         long out_px, float* ws, int H, int W, int C, int G, float eps, int silu, void* stream);

@@ -14,43 +14,60 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------- GroupNorm statistics
 // stage 1: per-channel sum / sum of squares of a slab of rows; stage 2: groups, in double.
+// The variance is E[x^2] - mean^2, so for a group whose mean is large against its spread (mean 12, std 1/4: mean^2 / var =
+// 2304) a relative error e of the sums is an error of 1152 e of rstd: they must be exact to fp32's last bit.  A thread
+// therefore adds GN_CHAIN rows in fp32 -- bf16 values have 8 significant bits and their squares 16, so 64 squares of values
+// of one binade (two binades of squares) add exactly in fp32's 24 -- and folds each chain into fp64, in which everything
+// after it runs.  (One fp32 chain over the slab, 512 rows at C = 2048, and the fp32 sum over the 256 rows of a pass at C = 8
+// lost the last bits of the squares' sum: tests/test_hip_vae_kernels.py.)  64 and not fewer: every chain's end exposes one
+// load latency, which at C = 512 (128 rows per thread) was measured as 3 us of a 57 us launch with chains of 16.
 constexpr int GN_ROWS = 512;   // rows per stage-1 block
+constexpr int GN_CHAIN = 64;   // rows a thread adds in fp32 before it folds the sums into fp64
 
 __global__ void __launch_bounds__(256) gn_partial_kernel(const bf16_raw* __restrict__ x, long ld, long M, int C,
-                                                         float* __restrict__ part) {
+                                                         double* __restrict__ part) {
   const int tpr = C / 8;                          // threads per row (8 channels = 16 bytes each)
   const int rpp = 256 / tpr;                      // rows per pass
   const int cx = threadIdx.x % tpr, ry = threadIdx.x / tpr;
   const long r0 = (long)blockIdx.x * GN_ROWS;
   const long r1 = r0 + GN_ROWS < M ? r0 + GN_ROWS : M;
-  float s[8], q[8];
+  double sd[8], qd[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
+  for (int e = 0; e < 8; ++e) sd[e] = qd[e] = 0.0;
   if (ry < rpp)
-    for (long r = r0 + ry; r < r1; r += rpp) {
-      const uint4 u = *reinterpret_cast<const uint4*>(x + r * ld + cx * 8);
-      const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+    for (long rb = r0 + ry; rb < r1; rb += (long)GN_CHAIN * rpp) {
+      const long re = rb + (long)GN_CHAIN * rpp < r1 ? rb + (long)GN_CHAIN * rpp : r1;
+      float s[8], q[8];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float a = bf2f(w[e] & 0xffff), b = bf2f(w[e] >> 16);
-        s[2 * e] += a; q[2 * e] += a * a;
-        s[2 * e + 1] += b; q[2 * e + 1] += b * b;
+      for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
+      for (long r = rb; r < re; r += rpp) {
+        const uint4 u = *reinterpret_cast<const uint4*>(x + r * ld + cx * 8);
+        const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float a = bf2f(w[e] & 0xffff), b = bf2f(w[e] >> 16);
+          s[2 * e] += a; q[2 * e] += a * a;
+          s[2 * e + 1] += b; q[2 * e + 1] += b * b;
+        }
       }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { sd[e] += (double)s[e]; qd[e] += (double)q[e]; }
     }
-  // rows of the block -> one value per channel (LDS: [ry][C] x 2)
-  extern __shared__ float sh[];
-  float* ss = sh;
-  float* qq = sh + (size_t)rpp * C;
+  // rows of the block -> one value per channel (LDS: [ry][C] x 2, doubles.  One array used twice, to stay at the 16 KiB of the
+  // fp32 arrays, was measured slower: 59.9 against 58.5 us at 128 x 128 x 512)
+  extern __shared__ double sh[];
+  double* ss = sh;
+  double* qq = sh + (size_t)rpp * C;
   if (ry < rpp) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      ss[ry * C + cx * 8 + e] = s[e];
-      qq[ry * C + cx * 8 + e] = q[e];
+      ss[ry * C + cx * 8 + e] = sd[e];
+      qq[ry * C + cx * 8 + e] = qd[e];
     }
   }
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += 256) {
-    float a = 0.f, b = 0.f;
+    double a = 0.0, b = 0.0;
     for (int r = 0; r < rpp; ++r) {
       a += ss[r * C + c];
       b += qq[r * C + c];
@@ -61,7 +78,7 @@ __global__ void __launch_bounds__(256) gn_partial_kernel(const bf16_raw* __restr
 }
 
 // stats[g] = (mean, rstd) of group g; one block per group
-__global__ void __launch_bounds__(256) gn_finish_kernel(const float* __restrict__ part, float* __restrict__ stats, int nblk,
+__global__ void __launch_bounds__(256) gn_finish_kernel(const double* __restrict__ part, float* __restrict__ stats, int nblk,
                                                         int C, int G, long M, float eps) {
   __shared__ double rs[4], rq[4];
   const int g = blockIdx.x, cpg = C / G;
@@ -69,8 +86,8 @@ __global__ void __launch_bounds__(256) gn_finish_kernel(const float* __restrict_
   for (long i = threadIdx.x; i < (long)nblk * cpg; i += 256) {
     const long b = i / cpg;
     const int c = g * cpg + (int)(i - b * cpg);
-    s += (double)part[(b * 2 + 0) * C + c];
-    q += (double)part[(b * 2 + 1) * C + c];
+    s += part[(b * 2 + 0) * C + c];
+    q += part[(b * 2 + 1) * C + c];
   }
   s = wave_sum_d(s);
   q = wave_sum_d(q);
@@ -235,10 +252,11 @@ __global__ void __launch_bounds__(256) softmax_rows_kernel(const float* __restri
 
 }  // namespace
 
-extern "C" long mgx_group_norm_workspace(long M, int C, int G) { return (long)cdiv(M, GN_ROWS) * 2 * C + 2L * G; }
+// (fp32 elements: the stage-1 sums are doubles, two elements each, in front of the 2 G statistics)
+extern "C" long mgx_group_norm_workspace(long M, int C, int G) { return (long)cdiv(M, GN_ROWS) * 4 * C + 2L * G; }
 
 // y = [silu](GroupNorm(x)) for one image: x plain [M = H W][C] bf16 (leading dimension ld), G groups, affine gamma / beta [C]
-// bf16; out: see gn_apply_kernel.  ws: fp32 scratch of mgx_group_norm_workspace(M, C, G) elements.
+// bf16; out: see gn_apply_kernel.  ws: fp32 scratch of mgx_group_norm_workspace(M, C, G) elements, 8-byte aligned.
 extern "C" int mgx_group_norm_nhwc(const uint16_t* x, long ld, const uint16_t* gamma, const uint16_t* beta, uint16_t* out,
                                    long out_row, long out_px, float* ws, int H, int Wd, int C, int G, float eps, int silu,
                                    void* stream) {
@@ -246,13 +264,14 @@ extern "C" int mgx_group_norm_nhwc(const uint16_t* x, long ld, const uint16_t* g
   MGX_REQUIRE(C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0 && G > 0 && C % G == 0, "channels must be 8 .. 2048, a power of two times 8");
   MGX_REQUIRE(ld % 8 == 0 && out_row % 8 == 0 && out_px % 8 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0) &&
                   ((uintptr_t)gamma % 16 == 0) && ((uintptr_t)beta % 16 == 0), "16-byte addressable rows");
+  MGX_REQUIRE((uintptr_t)ws % 8 == 0, "the workspace must be 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const long M = (long)H * Wd;
   const int nblk = cdiv(M, GN_ROWS);
-  float* part = ws;
-  float* stats = ws + (long)nblk * 2 * C;
+  double* part = reinterpret_cast<double*>(ws);
+  float* stats = ws + (long)nblk * 4 * C;
   const int rpp = 256 / (C / 8);
-  gn_partial_kernel<<<nblk, 256, (size_t)2 * rpp * C * sizeof(float), st>>>(x, ld, M, C, part);
+  gn_partial_kernel<<<nblk, 256, (size_t)2 * rpp * C * sizeof(double), st>>>(x, ld, M, C, part);
   gn_finish_kernel<<<G, 256, 0, st>>>(part, stats, nblk, C, G, M, eps);
   const long total = M * (C / 8);
   const int grid = (int)((total + 255) / 256 < 256L * 16 ? (total + 255) / 256 : 256L * 16);

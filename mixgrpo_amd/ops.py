@@ -395,15 +395,16 @@ def conv3x3(xpad, Wt, bias, out, H, W, C, Cout, ones=None, ld_out=None):
                                  Cout, 0 if ones is None else 1, stream()))
 
 
-def group_norm(x, gamma, beta, out, H, W, C, G, silu, padded, eps=1e-6):
-    """out = [silu](GroupNorm(x)), x plain [H W, C]; `padded`: out is a zero-bordered [(H+2), (W+2), C] image (interior written)."""
+def group_norm(x, gamma, beta, out, H, W, C, G, silu, padded, eps=1e-6, ld=None):
+    """out = [silu](GroupNorm(x)), x plain [H W, C]; `padded`: out is a zero-bordered [(H+2), (W+2), C] image (interior written).
+    `ld`: x is the first C columns of a plain [H W, ld] matrix (a tensor whose data_ptr() is its first element)."""
     ws = scratch("group_norm", lib().mgx_group_norm_workspace(H * W, C, G), F32, x.device)
     if padded:
         o, out_row = out.view(-1)[(W + 2) * C + C:], (W + 2) * C
     else:
         o, out_row = out, W * C
-    check(lib().mgx_group_norm_nhwc(ptr(x), C, ptr(gamma), ptr(beta), o.data_ptr(), out_row, C, ptr(ws), H, W, C, G, eps,
-                                    1 if silu else 0, stream()))
+    check(lib().mgx_group_norm_nhwc(ptr(x) if ld is None else x.data_ptr(), C if ld is None else ld, ptr(gamma), ptr(beta),
+                                    o.data_ptr(), out_row, C, ptr(ws), H, W, C, G, eps, 1 if silu else 0, stream()))
 
 
 def upsample2x_pad(x, outpad, H, W, C):

@@ -181,16 +181,23 @@ class AutoencoderKL:
         return x
 
     def _attention(self, name, x, H, W, C):
+        """x [H W, C] plain bf16 -> x + to_out(softmax(q k^T / sqrt(C)) v) of GroupNorm(x), in place: single-head attention over
+        the H W tokens, any H W up to 16384 (more is refused here, before anything is launched).  The GEMM writes S = q k^T with
+        a column count that is a multiple of 4, so for H W % 4 != 0 S gets up to three spare columns, computed from zeroed
+        spare k rows and never read by the softmax; the contraction of P v is zero-padded to a multiple of 64."""
         P, G = self.P, self.config.norm_num_groups
         M = H * W
         if M > 16384:
             raise ValueError("mid-block attention handles up to 16384 tokens (a 128 x 128 latent tile)")
+        M4 = (M + 3) // 4 * 4
         n = self._plain("attn_n", M, C)
         ops.group_norm(x, P[name + ".group_norm.weight"], P[name + ".group_norm.bias"], n, H, W, C, G, False, False)
-        qkv = self._plain("attn_qkv", M, 3 * C)
-        ops.gemm(Rows.of(n), P[name + ".qkv.weight"], P[name + ".qkv.bias"], Rows.of(qkv), 3 * C, C)
-        S = self._plain("attn_s", M, M, F32)
-        ops.gemm(Rows(qkv, M, 3 * C), qkv[0, C:], None, Rows.of(S), M, C, EPI_F32_ACC, beta=0.0, ldw=3 * C)     # q k^T, fp32
+        qkv = self._plain("attn_qkv", M4, 3 * C)
+        if M4 != M:
+            qkv[M:].zero_()
+        ops.gemm(Rows.of(n), P[name + ".qkv.weight"], P[name + ".qkv.bias"], Rows(qkv, M, 3 * C), 3 * C, C)
+        S = self._plain("attn_s", M, M4, F32)
+        ops.gemm(Rows(qkv, M, 3 * C), qkv[0, C:], None, Rows.of(S), M4, C, EPI_F32_ACC, beta=0.0, ldw=3 * C)    # q k^T, fp32
         Pm = self._plain("attn_p", M, M)
         ops.softmax_rows(S, Pm, M, M, float(C) ** -0.5)
         Mp = (M + 63) // 64 * 64

@@ -16,8 +16,8 @@ def _rel(a, b):
 
 @pytest.mark.parametrize("H,W,C,Cout", [(16, 16, 64, 64),        # 128x128-tile kernel, one K-tile per tap
                                          (24, 20, 128, 64),       # ragged rows: W not a multiple of anything
-                                         (128, 128, 256, 256),    # 256x256 persistent kernel (256 tiles), 4 K-tiles per tap
-                                         (64, 128, 512, 512),     # 8 K-tiles per tap
+                                         (128, 128, 256, 256),    # 64 tiles of 256x256: still the 128x128 kernel; 4 K-tiles per tap
+                                         (64, 128, 512, 512),     # 8 K-tiles per tap; 64 tiles again (tests/test_vae_refs.py)
                                          (32, 32, 128, 4)])       # conv_out's shape: 4 output channels, generic epilogue
 def test_conv3x3_implicit_gemm_vs_torch(H, W, C, Cout):
     from mixgrpo_amd import ops
