@@ -14,7 +14,7 @@ extern "C" const char* mgx_last_error(void) { return g_err; }
 // 100 * major + minor of the C ABI; NEGATIVE for a diagnostic build (common.h): such a library computes wrong results on
 // purpose and the host binding refuses to load it
 #ifdef MGX_DIAGNOSTIC_BUILD
-extern "C" int mgx_version(void) { return -101; }
+extern "C" int mgx_version(void) { return -102; }
 #else
-extern "C" int mgx_version(void) { return 101; }
+extern "C" int mgx_version(void) { return 102; }
 #endif

@@ -21,6 +21,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -645,6 +646,74 @@ __device__ __forceinline__ void persist_epilogue(const GemmArgs& g, f32x4 (&acc)
   if (EPI == EPI_F32_ACC) {
     float* Cb = reinterpret_cast<float*>(g.C);
     const bool rmw = g.beta != 0.f;
+    // ---- batched form (the shape of the 16-byte bf16 path below), for a wave whose 128 x 64 block lies wholly inside the matrix,
+    // in ONE batch of C and within 4 GiB of its first element -- all but the edge tiles.  Every address is a wave-uniform base
+    // (scalar registers) + one 32-bit per-lane byte offset; the old values are requested in 2-row batches, two batches ahead
+    // and BEFORE the stores of the batch in hand, so the wait for a batch's loads leaves the previous batch's stores in flight
+    // (vmcnt counts in issue order).  No masks: a store under a branch may be skipped, so hipcc counts it as absent, and the
+    // next wait -- too small by the stores that did run -- drains them after all.  beta == 0 reads nothing.
+    {
+      const int wu = __builtin_amdgcn_readfirstlane(wid);
+      const long mu = m0 + (wu >> 2) * 128, nu = n0 + (wu & 3) * 64;
+      const uint32_t rpb = (uint32_t)g.c.rpb, bu = (uint32_t)mu / rpb;
+      if (mu + 128 <= g.M && nu + 64 <= g.N && (uint32_t)(mu + 127) / rpb == bu && (127 * g.c.ld + 64) * 4 < (1L << 32)) {
+        char* cb = reinterpret_cast<char*>(Cb) + ((long)bu * g.c.bstride + (long)((uint32_t)mu - bu * rpb) * g.c.ld + nu) * 4;
+        const uint32_t ldc4 = (uint32_t)(g.c.ld * 4);
+        auto run = [&](auto rmw_c) {                  // beta != 0 / beta == 0: two straight-line copies, chosen wave-uniformly
+          constexpr bool RMW = decltype(rmw_c)::value;
+          float4 old[2][2][RMW ? 4 : 1];              // [ring slot][row of the 2-row batch][column group]
+          // `dep`: an opaque zero that depends on the previous batch's results (keeps hipcc from hoisting every load to the top)
+          auto load_old = [&](int h, int j0, uint32_t dep) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const char* rp = cb + (((uint32_t)(fr + 16 * (j0 + k)) + dep) * ldc4 + fq * 32);    // + lane_feat(0, t) * 4: immediates
+#pragma unroll
+              for (int t = 0; t < 4; ++t) old[h][k][RMW ? t : 0] = *reinterpret_cast<const float4*>(rp + lane_feat(0, t) * 4);
+            }
+          };
+          if (RMW) {
+            load_old(0, 0, 0);
+            load_old(1, 2, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int jb = 0; jb < MT; jb += 2) {
+            const int slot = (jb >> 1) & 1;
+            float4 o[2][4];
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+              for (int t = 0; t < 4; ++t) {
+                const f32x4 a = acc[t][jb + jj];
+                o[jj][t] = make_float4(a[0], a[1], a[2], a[3]);
+                if (RMW) {                            // one v_fma_f32 each (not v_pk_fma_f32: profiles/r04_gemm_noslp_ab.log)
+                  const float4 q = old[slot][jj][RMW ? t : 0];
+                  o[jj][t].x = vfma1(g.beta, q.x, o[jj][t].x);
+                  o[jj][t].y = vfma1(g.beta, q.y, o[jj][t].y);
+                  o[jj][t].z = vfma1(g.beta, q.z, o[jj][t].z);
+                  o[jj][t].w = vfma1(g.beta, q.w, o[jj][t].w);
+                }
+              }
+            if (RMW && jb + 4 < MT) {                 // rows jb + 4, jb + 5 into the slot just consumed
+              uint32_t dep = 0;
+              asm volatile("" : "+v"(dep) : "v"(o[1][3].w));
+              load_old(slot, jb + 4, dep);
+            }
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+              char* rp = cb + ((uint32_t)(fr + 16 * (jb + jj)) * ldc4 + fq * 32);
+#pragma unroll
+              for (int t = 0; t < 4; ++t) *reinterpret_cast<float4*>(rp + lane_feat(0, t) * 4) = o[jj][t];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        };
+        if (rmw) run(std::true_type{});
+        else run(std::false_type{});
+        return;
+      }
+    }
+    // ---- general form (edge blocks; rows that cross a batch boundary of C or lie 4 GiB apart): masked, 64-bit offsets row by row
     bool nok[4];
     long ncol[4];
 #pragma unroll
@@ -921,6 +990,16 @@ __global__ void __launch_bounds__(64) gemm_sk_fixup_kernel(GemmArgs g, int nw) {
 // of the late half during the early half's MA of k, one barrier before the first LB of k).  vmcnt(8) at the end of LB leaves
 // this K-tile's eight pieces in flight: everything K-tile k+1 reads has landed in every wave before the barrier in front of
 // the first LA of k+1.
+// The hand-over between output tiles: the FIRST K-tile of a unit does not wait at the end of its LB.  vmcnt counts the epilogue's
+// stores too, they are older than the eight pieces that wait leaves in flight, and it was spent waiting for their
+// acknowledgements (2 - 3 % of a K = 3072 launch, profiles/gemm_handover_ab.log).  What that wait protects -- K-tile 1 of the
+// unit, read from the first LA of kt = 1 on -- is instead awaited by every wave BEFORE its epilogue (vmcnt(0) behind the last
+// MB: the pieces issued in the previous unit's last K-tile, one K-tile old by then; the first unit: the prologue's vmcnt(0)),
+// and every wave passes the four barriers of kt = 0 (the early half: at least three of them after the late half's wait)
+// before any wave reads K-tile 1.  No order between loads and stores is assumed: the wait in front of the stores is a full
+// one, and the next counted wait (end of LB of kt = 1) has the stores in front of everything it needs, as every wait had.
+// The DMA issue points and their targets are unchanged, so the stage-reuse argument above holds as it stands (the q | k norm
+// epilogue's `red` is the A stage kt = 0 fills in its LA, as before).
 // Measured (profiles/r02_pp_clock.log, in-kernel clock = d s_memtime / d s_memrealtime): 2423-2476 shader cycles per K-tile
 // against the matrix pipe's 2048 (83-85 % busy) at a clock the chip holds at 1.71-1.76 GHz under this load; the first
 // version of this loop with FOUR phases of 16 MFMAs (8 barriers per K-tile) ran 2622-2703 cycles at 1.82-1.87 GHz and
@@ -1071,7 +1150,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) PGLDS(wb_, cw[k], lw_ + k * RS * 128);
       PIN();
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      if (kt != 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // (kt == 0: K-tile 1 landed before the epilogue: see above)
       BAR();
       // ---- MB: tokens 64-127 x features 0-63
       __builtin_amdgcn_s_setprio(1);
@@ -1088,6 +1167,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
     }
     int el = lane, ew = wid;
     asm volatile("" : "+v"(el), "+v"(ew));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next unit's K-tile 1 has landed: its kt = 0 need not wait behind our stores
     // (measured on the four-phase version and dropped: both halves running their epilogues in the SAME barrier interval --
     //  one extra barrier per half and tile -- is neutral; `s_setprio` around the MFMA sections is worth 2 %)
     if (SK && partial) {
@@ -1107,8 +1187,17 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(GemmArgs g) {
     ++ui;
     u_tile = n_tile; kbeg = nkbeg; kend = nkend; partial = npartial;
     m0 = nm0; n0 = nn0;
+    if constexpr (EPI == EPI_BIAS_GATE_RES) {
+      // this epilogue needs every register: the new tile's offsets are formed again instead of kept alive across it (spills
+      // and their reloads in the epilogue otherwise; 2 % at K = 3072, profiles/gemm_handover_ab.log.  The q | k norm epilogues
+      // spill 8 - 12 bytes without it and measure the same either way: they keep the copy)
+      long rm0 = m0, rn0 = n0;
+      asm volatile("" : "+s"(rm0), "+s"(rn0));
+      TILE_OFFS(rm0, rn0, ao, wo);
+    } else {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { ao[k] = nao[k]; wo[k] = nwo[k]; }
+      for (int k = 0; k < 4; ++k) { ao[k] = nao[k]; wo[k] = nwo[k]; }
+    }
   }
   if (!late) __builtin_amdgcn_s_barrier();         // matches the late half's last barrier
 #undef UNIT
