@@ -388,6 +388,11 @@ def lora_merge(W0, Bt, A, W16, N, K, r, s):
 
 
 # ------------------------------------------------------------------------------------------------ VAE decode (csrc/vae.hip)
+def _interior(outpad, W, C):
+    """The zero-bordered [(H+2), (W+2), C] image `outpad` from its first interior pixel on: one row and one pixel in"""
+    return outpad.view(-1)[(W + 2) * C + C:]
+
+
 def conv3x3(xpad, Wt, bias, out, H, W, C, Cout, ones=None, ld_out=None):
     """out[H W, Cout] (+)= conv3x3(xpad) + bias: xpad zero-bordered NHWC [(H+2), (W+2), C], Wt [Cout, 3, 3, C].
     `ones` given: the residual form out = bf16(out + bf16(conv + bias))."""
@@ -400,7 +405,7 @@ def group_norm(x, gamma, beta, out, H, W, C, G, silu, padded, eps=1e-6, ld=None)
     `ld`: x is the first C columns of a plain [H W, ld] matrix (a tensor whose data_ptr() is its first element)."""
     ws = scratch("group_norm", lib().mgx_group_norm_workspace(H * W, C, G), F32, x.device)
     if padded:
-        o, out_row = out.view(-1)[(W + 2) * C + C:], (W + 2) * C
+        o, out_row = _interior(out, W, C), (W + 2) * C
     else:
         o, out_row = out, W * C
     check(lib().mgx_group_norm_nhwc(ptr(x) if ld is None else x.data_ptr(), C if ld is None else ld, ptr(gamma), ptr(beta),
@@ -409,11 +414,11 @@ def group_norm(x, gamma, beta, out, H, W, C, G, silu, padded, eps=1e-6, ld=None)
 
 def upsample2x_pad(x, outpad, H, W, C):
     """plain [H W, C] -> interior of the zero-bordered [(2H+2), (2W+2), C] image `outpad`"""
-    check(lib().mgx_upsample2x_pad_nhwc(ptr(x), outpad.view(-1)[(2 * W + 2) * C + C:].data_ptr(), H, W, C, stream()))
+    check(lib().mgx_upsample2x_pad_nhwc(ptr(x), _interior(outpad, 2 * W, C).data_ptr(), H, W, C, stream()))
 
 
 def latents_to_pad(z, outpad, Cin, H, W, C):
-    check(lib().mgx_latents_to_pad_nhwc(ptr(z), outpad.view(-1)[(W + 2) * C + C:].data_ptr(), Cin, H, W, C, stream()))
+    check(lib().mgx_latents_to_pad_nhwc(ptr(z), _interior(outpad, W, C).data_ptr(), Cin, H, W, C, stream()))
 
 
 def nhwc_to_image(x, ld, img, Cout, H, W):
@@ -429,7 +434,7 @@ def conv3x3s2(xpad, Wt, bias, out, H, W, C, Cout, ld_out=None):
 
 def pad_nhwc(x, ld, outpad, H, W, C):
     """first C channels of plain [H W, ld] -> interior of the zero-bordered [(H+2), (W+2), C] image `outpad`"""
-    check(lib().mgx_pad_nhwc(ptr(x), ld, outpad.view(-1)[(W + 2) * C + C:].data_ptr(), H, W, C, stream()))
+    check(lib().mgx_pad_nhwc(ptr(x), ld, _interior(outpad, W, C).data_ptr(), H, W, C, stream()))
 
 
 def diag_gaussian(moments, ld, noise, mean, std, sample, Cz, H, W):

@@ -12,9 +12,11 @@ follows `spatial_tiled_encode` (autoencoder_kl_causal_3d.py:408-470): the MOMENT
 Layout: one image at a time, activations NHWC bf16; every 3x3 convolution is an implicit GEMM on the MFMA GEMM kernels over a
 zero-bordered copy written by the GroupNorm + SiLU (or upsample) pass in front of it, residual sums ride the GEMM epilogue, the
 mid block's single-head attention (H W <= 16384 tokens of dim 512) is two GEMMs around an fp32 row softmax.  All arithmetic is in
-csrc/ (gemm.hip, vae.hip); this file sequences it.  Tiling follows the reference lineage's `spatial_tiled_decode`
+csrc/ (gemm.hip, vae.hip); this file sequences it, walking the layer list of mixgrpo_amd/vae_arch.py, which also gives the
+key inventory of both halves.  Tiling follows the reference lineage's `spatial_tiled_decode`
 (fastvideo/models/hunyuan/vae/autoencoder_kl_causal_3d.py:472-525): a 1024^2 image (128^2 latent) is exactly one tile and is
-decoded whole; larger images are decoded tile by tile and blended (in place on the later tile, :384-399).
+decoded whole; larger images are decoded tile by tile and blended (in place on the later tile, :384-399).  That tiling is
+pinned to the reference's vendored 3-D lineage; parity with diffusers' AutoencoderKL.tiled_decode is unpinned.
 """
 import json
 import os
@@ -25,6 +27,7 @@ import torch
 
 from . import ops
 from .ops import BF16, F32, Rows, EPI_BIAS, EPI_BIAS_GATE_RES, EPI_F32_ACC
+from .vae_arch import HALVES, layers, param_shapes
 
 
 @dataclass
@@ -96,22 +99,20 @@ class AutoencoderKL:
         dict with none or only some of them gives a decoder-only object: `has_encoder` False); quant-conv entries are ignored.
         Conv weights OIHW -> [O][kh][kw][I] bf16 with the input channels padded to the kernel's tap width and the output
         channels to a multiple of 4."""
-        c = self.config
-        need = _decoder_keys(c)
-        missing = [k for k in need if k not in sd]
-        if missing:
-            raise KeyError(f"VAE state dict lacks {len(missing)} decoder tensors, e.g. {missing[:3]}")
         P = {}
-        self._convert(sd, need, "decoder", P)
-        enc = _encoder_keys(c)
-        self.has_encoder = all(k in sd for k in enc)
-        if self.has_encoder:
-            self._convert(sd, enc, "encoder", P)
+        for half in HALVES:
+            keys = list(param_shapes(self.config, half))
+            missing = [k for k in keys if k not in sd]
+            if missing and half == "decoder":
+                raise KeyError(f"VAE state dict lacks {len(missing)} decoder tensors, e.g. {missing[:3]}")
+            if not missing:
+                self._convert(sd, keys, half, P)
+        self.has_encoder = any(k.startswith("encoder.") for k in P)
         self.P = P
         return self
 
     def _convert(self, sd, keys, half, P):
-        c, dev = self.config, self.device
+        dev = self.device
         for k in keys:
             t = sd[k].to(dev)
             if t.dim() == 4 and t.shape[-1] == 3:
@@ -128,8 +129,7 @@ class AutoencoderKL:
                 P[k] = b
             else:
                 P[k] = t.to(BF16).contiguous()
-        a = half + ".mid_block.attentions.0"
-        if c.mid_block_add_attention:
+        for a in (l.name for l in layers(self.config, half) if l.kind == "attention"):      # q | k | v as one GEMM operand
             P[a + ".qkv.weight"] = torch.cat([P[f"{a}.to_{n}.weight"] for n in "qkv"], 0).contiguous()
             P[a + ".qkv.bias"] = torch.cat([P[f"{a}.to_{n}.bias"] for n in "qkv"], 0).contiguous()
 
@@ -137,9 +137,9 @@ class AutoencoderKL:
         """Random bf16 weights of the configured architecture (no checkpoint offline); the decoder's from the same generator as
         oracle/vae.py, the encoder's from a second one (seed + 1) drawn after them, so the decoder's do not depend on it."""
         sd = {}
-        for shapes, half_seed in ((_decoder_shapes(self.config), seed), (_encoder_shapes(self.config), seed + 1)):
-            g = torch.Generator().manual_seed(half_seed)
-            for k, shp in shapes.items():
+        for i, half in enumerate(HALVES):
+            g = torch.Generator().manual_seed(seed + i)
+            for k, shp in param_shapes(self.config, half).items():
                 if k.endswith(".weight") and len(shp) == 1:
                     sd[k] = (1.0 + 0.1 * torch.randn(shp, generator=g)).to(BF16)
                 elif k.endswith(".bias"):
@@ -217,88 +217,65 @@ class AutoencoderKL:
                  gate=self._ones, gate_ld=0)
         return x
 
-    def _decoder(self, z):
-        """z [latent_channels, h, w] fp32 on the device -> image [out_channels, 8h, 8w] bf16"""
-        c, P = self.config, self.P
-        if P is None:
-            raise RuntimeError("VAE weights not loaded")
-        ch = list(reversed(c.block_out_channels))
-        _, H, W = z.shape
-        Cz = _pad_ch(c.latent_channels)
-        # its own buffer: only the first `latent_channels` of its Cz channels are ever written, the rest must stay the zeros of
-        # the allocation (conv_in's weight is zero there, but 0 * inf = NaN) -- the shared ("pad", H, W, 64) buffer of a
-        # 64-channel layer at the same resolution would leave stale activations in them
-        pad = self._padded(H, W, Cz, tag="pad_z")
-        ops.latents_to_pad(z.contiguous(), pad, c.latent_channels, H, W, Cz)
-        x = self._plain("x", H * W, ch[0])
-        ops.conv3x3(pad, P["decoder.conv_in.weight"], P["decoder.conv_in.bias"], x, H, W, Cz, ch[0])
-        x = self._resnet("decoder.mid_block.resnets.0", x, H, W, ch[0], ch[0])
-        if c.mid_block_add_attention:
-            x = self._attention("decoder.mid_block.attentions.0", x, H, W, ch[0])
-        x = self._resnet("decoder.mid_block.resnets.1", x, H, W, ch[0], ch[0])
-        prev = ch[0]
-        for i, co in enumerate(ch):
-            for j in range(c.layers_per_block + 1):
-                x = self._resnet(f"decoder.up_blocks.{i}.resnets.{j}", x, H, W, prev if j == 0 else co, co)
-            if i != len(ch) - 1:
+    def _walk(self, half, t):
+        """One image through the layers of `half`: t [C, H, W] fp32 on the device -> the decoder's image [out_channels, H', W']
+        bf16, or the encoder's moments (see `_encoder`).  Both results are fresh tensors, not shared buffers: a batch stacks
+        them and the tiling keeps several."""
+        P, G = self.P, self.config.norm_num_groups
+        _, H, W = t.shape
+        for kind, name, ci, co in layers(self.config, half):
+            if kind == "conv_in":
+                # its own buffer: only the first `ci` of its Cp channels are ever written, the rest must stay the zeros of the
+                # allocation (conv_in's weight is zero there, but 0 * inf = NaN) -- the shared ("pad", H, W, 64) buffer of a
+                # 64-channel layer at the same resolution would leave stale activations in them
+                Cp = _pad_ch(ci)
+                pad = self._padded(H, W, Cp, tag="pad_z" if half == "decoder" else "pad_x")
+                ops.latents_to_pad(t.contiguous(), pad, ci, H, W, Cp)
+                x = self._plain("x", H * W, co)
+                ops.conv3x3(pad, P[name + ".weight"], P[name + ".bias"], x, H, W, Cp, co)
+            elif kind == "resnet":
+                x = self._resnet(name, x, H, W, ci, co)
+            elif kind == "attention":
+                x = self._attention(name, x, H, W, ci)
+            elif kind == "upsample":
                 pad = self._padded(2 * H, 2 * W, co)
                 ops.upsample2x_pad(x, pad, H, W, co)
                 H, W = 2 * H, 2 * W
-                y = self._plain("x", H * W, co)
-                k = f"decoder.up_blocks.{i}.upsamplers.0.conv"
-                ops.conv3x3(pad, P[k + ".weight"], P[k + ".bias"], y, H, W, co, co)
-                x = y
-            prev = co
-        pad = self._padded(H, W, ch[-1])
-        ops.group_norm(x, P["decoder.conv_norm_out.weight"], P["decoder.conv_norm_out.bias"], pad, H, W, ch[-1],
-                       c.norm_num_groups, True, True)
-        Co = (c.out_channels + 3) // 4 * 4
-        y = self._plain("img_nhwc", H * W, 8)
-        ops.conv3x3(pad, P["decoder.conv_out.weight"], P["decoder.conv_out.bias"], y, H, W, ch[-1], Co, ld_out=8)
-        img = torch.empty(c.out_channels, H, W, dtype=BF16, device=self.device)
-        ops.nhwc_to_image(y, 8, img, c.out_channels, H, W)
-        return img
+                x = self._plain("x", H * W, co)
+                ops.conv3x3(pad, P[name + ".weight"], P[name + ".bias"], x, H, W, co, co)
+            elif kind == "downsample":                           # Downsample2D(padding=0): pad right / bottom, 3x3 stride 2
+                pad = self._padded(H, W, co)
+                ops.pad_nhwc(x, co, pad, H, W, co)
+                y = self._plain("x", (H // 2) * (W // 2), co)
+                ops.conv3x3s2(pad, P[name + ".weight"], P[name + ".bias"], y, H, W, co, co)
+                H, W, x = H // 2, W // 2, y
+            elif kind == "norm_out":
+                pad = self._padded(H, W, ci)
+                ops.group_norm(x, P[name + ".weight"], P[name + ".bias"], pad, H, W, ci, G, True, True)
+            elif half == "decoder":                              # conv_out, to NHWC rows of 8 and from there to the image
+                y = self._plain("img_nhwc", H * W, 8)
+                ops.conv3x3(pad, P[name + ".weight"], P[name + ".bias"], y, H, W, ci, (co + 3) // 4 * 4, ld_out=8)
+                out = torch.empty(co, H, W, dtype=BF16, device=self.device)
+                ops.nhwc_to_image(y, 8, out, co, H, W)
+            else:                                                # conv_out, onto the moments
+                out = torch.empty(H * W, co, dtype=BF16, device=self.device)
+                ops.conv3x3(pad, P[name + ".weight"], P[name + ".bias"], out, H, W, ci, co)
+        return out
+
+    def _decoder(self, z):
+        """z [latent_channels, h, w] fp32 on the device -> image [out_channels, 8h, 8w] bf16"""
+        if self.P is None:
+            raise RuntimeError("VAE weights not loaded")
+        return self._walk("decoder", z)
 
     def _encoder(self, x):
         """x [in_channels, H, W] fp32 on the device -> the moments, plain NHWC bf16 [(H / f)(W / f)][2 latent_channels] with
         f = 2^(len(block_out_channels) - 1): channels [0, latent_channels) the mean, the rest the logvar."""
-        c, P = self.config, self.P
-        ch = list(c.block_out_channels)
-        f = 2 ** (len(ch) - 1)
+        f = 2 ** (len(self.config.block_out_channels) - 1)
         _, H, W = x.shape
         if H % f or W % f or H <= 0 or W <= 0:
             raise ValueError(f"the encoder takes image sides that are multiples of {f}, not {H} x {W}")
-        Ci = _pad_ch(c.in_channels)
-        # its own buffer, like the decoder's pad_z: only the first `in_channels` of its Ci channels are ever written
-        pad = self._padded(H, W, Ci, tag="pad_x")
-        ops.latents_to_pad(x.contiguous(), pad, c.in_channels, H, W, Ci)
-        y = self._plain("x", H * W, ch[0])
-        ops.conv3x3(pad, P["encoder.conv_in.weight"], P["encoder.conv_in.bias"], y, H, W, Ci, ch[0])
-        x = y
-        prev = ch[0]
-        for i, co in enumerate(ch):
-            for j in range(c.layers_per_block):
-                x = self._resnet(f"encoder.down_blocks.{i}.resnets.{j}", x, H, W, prev if j == 0 else co, co)
-            if i != len(ch) - 1:                                 # Downsample2D(padding=0): pad right / bottom, 3x3 stride 2
-                pad = self._padded(H, W, co)
-                ops.pad_nhwc(x, co, pad, H, W, co)
-                k = f"encoder.down_blocks.{i}.downsamplers.0.conv"
-                y = self._plain("x", (H // 2) * (W // 2), co)
-                ops.conv3x3s2(pad, P[k + ".weight"], P[k + ".bias"], y, H, W, co, co)
-                H, W = H // 2, W // 2
-                x = y
-            prev = co
-        x = self._resnet("encoder.mid_block.resnets.0", x, H, W, prev, prev)
-        if c.mid_block_add_attention:
-            x = self._attention("encoder.mid_block.attentions.0", x, H, W, prev)
-        x = self._resnet("encoder.mid_block.resnets.1", x, H, W, prev, prev)
-        pad = self._padded(H, W, prev)
-        ops.group_norm(x, P["encoder.conv_norm_out.weight"], P["encoder.conv_norm_out.bias"], pad, H, W, prev,
-                       c.norm_num_groups, True, True)
-        Cm = 2 * c.latent_channels
-        mom = torch.empty(H * W, Cm, dtype=BF16, device=self.device)      # (not a shared buffer: tiled_encode keeps several)
-        ops.conv3x3(pad, P["encoder.conv_out.weight"], P["encoder.conv_out.bias"], mom, H, W, prev, Cm)
-        return mom
+        return self._walk("encoder", x)
 
     # ---------------------------------------------------------------------------------------------- public surface
     def enable_tiling(self, use_tiling=True):
@@ -311,26 +288,9 @@ class AutoencoderKL:
         return torch.stack([self._decoder(z[b].float()) for b in range(z.shape[0])])
 
     def tiled_decode(self, z):
-        """autoencoder_kl_causal_3d.py:472-525 in 2-D; the blends are bf16 tensor arithmetic on the tiles, row by row, IN PLACE
-        on the later tile exactly as :384-399 (the tile above / to the left has already been blended itself)."""
+        """autoencoder_kl_causal_3d.py:472-525 in 2-D: latent tiles of `tile_latent_min_size`, their images blended and cropped."""
         tl, ts, ov = self.tile_latent_min_size, self.tile_sample_min_size, self.tile_overlap_factor
-        overlap_size = int(tl * (1 - ov))
-        blend_extent = int(ts * ov)
-        row_limit = ts - blend_extent
-        rows = []
-        for i in range(0, z.shape[-2], overlap_size):
-            rows.append([self._decode_batch(z[:, :, i:i + tl, j:j + tl]) for j in range(0, z.shape[-1], overlap_size)])
-        result_rows = []
-        for i, row in enumerate(rows):
-            result_row = []
-            for j, tile in enumerate(row):
-                if i > 0:
-                    tile = _blend(rows[i - 1][j], tile, blend_extent, -2)
-                if j > 0:
-                    tile = _blend(row[j - 1], tile, blend_extent, -1)
-                result_row.append(tile[..., :row_limit, :row_limit])
-            result_rows.append(torch.cat(result_row, dim=-1))
-        return torch.cat(result_rows, dim=-2)
+        return _tiled(z, tl, int(tl * (1 - ov)), int(ts * ov), ts - int(ts * ov), -2, -1, self._decode_batch)
 
     @torch.no_grad()
     def decode(self, z, return_dict=True, generator=None):
@@ -351,25 +311,9 @@ class AutoencoderKL:
 
     def _tiled_moments(self, x):
         """autoencoder_kl_causal_3d.py:408-462 in 2-D, on NHWC moments (rows are dim 1, columns dim 2): image tiles of
-        `tile_sample_min_size`, their moments blended in place on the later tile and cropped as in `tiled_decode`."""
+        `tile_sample_min_size`, their moments blended and cropped."""
         tl, ts, ov = self.tile_latent_min_size, self.tile_sample_min_size, self.tile_overlap_factor
-        overlap_size = int(ts * (1 - ov))
-        blend_extent = int(tl * ov)
-        row_limit = tl - blend_extent
-        rows = []
-        for i in range(0, x.shape[-2], overlap_size):
-            rows.append([self._encode_batch(x[:, :, i:i + ts, j:j + ts]) for j in range(0, x.shape[-1], overlap_size)])
-        result_rows = []
-        for i, row in enumerate(rows):
-            result_row = []
-            for j, tile in enumerate(row):
-                if i > 0:
-                    tile = _blend(rows[i - 1][j], tile, blend_extent, 1)
-                if j > 0:
-                    tile = _blend(row[j - 1], tile, blend_extent, 2)
-                result_row.append(tile[:, :row_limit, :row_limit])
-            result_rows.append(torch.cat(result_row, dim=2))
-        return torch.cat(result_rows, dim=1)
+        return _tiled(x, ts, int(ts * (1 - ov)), int(tl * ov), tl - int(tl * ov), 1, 2, self._encode_batch)
 
     def _check_encode(self):
         c = self.config
@@ -381,16 +325,17 @@ class AutoencoderKL:
         if not self.has_encoder:
             raise RuntimeError("this VAE is decoder-only: its state dict did not hold every encoder.* tensor, so it has no encoder")
 
+    def _posterior(self, mom, return_dict):
+        dist = DiagonalGaussianDistribution(mom, self.config.latent_channels)
+        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+
     @torch.no_grad()
     def tiled_encode(self, x, return_dict=True, return_moments=False):
         """`spatial_tiled_encode` (autoencoder_kl_causal_3d.py:408-470): one Gaussian over the blended moments (:466), or --
         `return_moments` (:463-464) -- the moments themselves, [B, 2 latent_channels, h, w]."""
         self._check_encode()
         mom = self._tiled_moments(x.to(self.device))
-        if return_moments:
-            return mom.permute(0, 3, 1, 2)
-        dist = DiagonalGaussianDistribution(mom, self.config.latent_channels)
-        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+        return mom.permute(0, 3, 1, 2) if return_moments else self._posterior(mom, return_dict)
 
     @torch.no_grad()
     def encode(self, x, return_dict=True):
@@ -400,12 +345,8 @@ class AutoencoderKL:
         self._check_encode()
         x = x.to(self.device)
         ts = self.tile_sample_min_size
-        if self.use_tiling and (x.shape[-1] > ts or x.shape[-2] > ts):
-            mom = self._tiled_moments(x)
-        else:
-            mom = self._encode_batch(x)
-        dist = DiagonalGaussianDistribution(mom, self.config.latent_channels)
-        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+        tiled = self.use_tiling and (x.shape[-1] > ts or x.shape[-2] > ts)
+        return self._posterior(self._tiled_moments(x) if tiled else self._encode_batch(x), return_dict)
 
 
 class AutoencoderKLOutput:
@@ -461,92 +402,22 @@ def _blend(a, b, blend_extent, dim):
     return b
 
 
-def _decoder_shapes(cfg):
-    ch = list(reversed(cfg.block_out_channels))
-    out = {}
-
-    def conv(name, co, ci, k):
-        out[name + ".weight"] = (co, ci, k, k)
-        out[name + ".bias"] = (co,)
-
-    def norm(name, c):
-        out[name + ".weight"] = (c,)
-        out[name + ".bias"] = (c,)
-
-    def resnet(name, ci, co):
-        norm(name + ".norm1", ci)
-        conv(name + ".conv1", co, ci, 3)
-        norm(name + ".norm2", co)
-        conv(name + ".conv2", co, co, 3)
-        if ci != co:
-            conv(name + ".conv_shortcut", co, ci, 1)
-
-    conv("decoder.conv_in", ch[0], cfg.latent_channels, 3)
-    resnet("decoder.mid_block.resnets.0", ch[0], ch[0])
-    if cfg.mid_block_add_attention:
-        a = "decoder.mid_block.attentions.0"
-        norm(a + ".group_norm", ch[0])
-        for n in ("to_q", "to_k", "to_v", "to_out.0"):
-            out[f"{a}.{n}.weight"] = (ch[0], ch[0])
-            out[f"{a}.{n}.bias"] = (ch[0],)
-    resnet("decoder.mid_block.resnets.1", ch[0], ch[0])
-    prev = ch[0]
-    for i, co in enumerate(ch):
-        for j in range(cfg.layers_per_block + 1):
-            resnet(f"decoder.up_blocks.{i}.resnets.{j}", prev if j == 0 else co, co)
-        if i != len(ch) - 1:
-            conv(f"decoder.up_blocks.{i}.upsamplers.0.conv", co, co, 3)
-        prev = co
-    norm("decoder.conv_norm_out", ch[-1])
-    conv("decoder.conv_out", cfg.out_channels, ch[-1], 3)
-    return out
-
-
-def _decoder_keys(cfg):
-    return list(_decoder_shapes(cfg))
-
-
-def _encoder_shapes(cfg):
-    """diffusers key -> shape for the encoder half; `i` runs in the forward order of `block_out_channels`."""
-    ch = list(cfg.block_out_channels)
-    out = {}
-
-    def conv(name, co, ci, k):
-        out[name + ".weight"] = (co, ci, k, k)
-        out[name + ".bias"] = (co,)
-
-    def norm(name, c):
-        out[name + ".weight"] = (c,)
-        out[name + ".bias"] = (c,)
-
-    def resnet(name, ci, co):
-        norm(name + ".norm1", ci)
-        conv(name + ".conv1", co, ci, 3)
-        norm(name + ".norm2", co)
-        conv(name + ".conv2", co, co, 3)
-        if ci != co:
-            conv(name + ".conv_shortcut", co, ci, 1)
-
-    conv("encoder.conv_in", ch[0], cfg.in_channels, 3)
-    prev = ch[0]
-    for i, co in enumerate(ch):
-        for j in range(cfg.layers_per_block):
-            resnet(f"encoder.down_blocks.{i}.resnets.{j}", prev if j == 0 else co, co)
-        if i != len(ch) - 1:
-            conv(f"encoder.down_blocks.{i}.downsamplers.0.conv", co, co, 3)
-        prev = co
-    resnet("encoder.mid_block.resnets.0", prev, prev)
-    if cfg.mid_block_add_attention:
-        a = "encoder.mid_block.attentions.0"
-        norm(a + ".group_norm", prev)
-        for n in ("to_q", "to_k", "to_v", "to_out.0"):
-            out[f"{a}.{n}.weight"] = (prev, prev)
-            out[f"{a}.{n}.bias"] = (prev,)
-    resnet("encoder.mid_block.resnets.1", prev, prev)
-    norm("encoder.conv_norm_out", prev)
-    conv("encoder.conv_out", (2 if cfg.double_z else 1) * cfg.latent_channels, prev, 3)
-    return out
-
-
-def _encoder_keys(cfg):
-    return list(_encoder_shapes(cfg))
+def _tiled(t, tile, stride, blend_extent, limit, rows_dim, cols_dim, run):
+    """The tile walk of `spatial_tiled_decode` / `spatial_tiled_encode` (autoencoder_kl_causal_3d.py:472-525, 408-462) in 2-D:
+    `run` on the tiles of side `tile`, `stride` apart, of t [B, C, H, W]; each result blended over `blend_extent` rows /
+    columns (its dims `rows_dim` / `cols_dim`) with the one above and the one to its left -- bf16 tensor arithmetic IN PLACE
+    on the later tile exactly as :384-399, the earlier tile having been blended itself -- and cropped to `limit`."""
+    rows = [[run(t[:, :, i:i + tile, j:j + tile]) for j in range(0, t.shape[-1], stride)] for i in range(0, t.shape[-2], stride)]
+    crop = [slice(None)] * rows[0][0].dim()
+    crop[rows_dim] = crop[cols_dim] = slice(limit)
+    result_rows = []
+    for i, row in enumerate(rows):
+        result_row = []
+        for j, out in enumerate(row):
+            if i > 0:
+                out = _blend(rows[i - 1][j], out, blend_extent, rows_dim)
+            if j > 0:
+                out = _blend(row[j - 1], out, blend_extent, cols_dim)
+            result_row.append(out[tuple(crop)])
+        result_rows.append(torch.cat(result_row, dim=cols_dim))
+    return torch.cat(result_rows, dim=rows_dim)

@@ -4,10 +4,12 @@ What it restates: `vae.enable_tiling(); image = vae.decode(latents, return_dict=
 (fastvideo/train_grpo_flux.py:279-289) with `vae = AutoencoderKL.from_pretrained(..., subfolder="vae", torch_dtype=torch.bfloat16)`
 (:697-701) under `torch.autocast("cuda", dtype=torch.bfloat16)`.
 
-PINNED to the reference (tests/test_vae_oracle.py, fixtures tests/golden/vae_tiling.* produced by `gen_fixtures.py vae` running
-the reference's own code in place): the tile-size rule (its constructor, autoencoder_kl_causal_3d.py:132-139), `blend_v` /
-`blend_h` (:384-399) and the tile schedule + blended pixels of `spatial_tiled_decode` (:472-525, with a recording decoder
-stand-in) -- bit for bit, and `mixgrpo_amd/vae.py`'s tiling is held to the same fixtures.
+PINNED to the reference's vendored 3-D lineage (tests/test_vae_oracle.py, fixtures tests/golden/vae_tiling.* produced by
+`gen_fixtures.py vae` running the reference's own code in place): the tile-size rule (its constructor,
+autoencoder_kl_causal_3d.py:132-139), `blend_v` / `blend_h` (:384-399) and the tile schedule + blended pixels of
+`spatial_tiled_decode` (:472-525, with a recording decoder stand-in) -- bit for bit, and `mixgrpo_amd/vae.py`'s tiling is held
+to the same fixtures.  That file is the Hunyuan 3-D VAE's; the FLUX path of the reference calls `enable_tiling()` on diffusers'
+2-D AutoencoderKL, so parity with diffusers' AutoencoderKL.tiled_decode (its tile-size rule, blends, schedule) is unpinned.
 PARITY UNPINNED for everything inside a tile -- convolutions, GroupNorm, SiLU, the mid block's attention, upsampling, the
 channel configuration: `AutoencoderKL` lives in diffusers (0.32.x per the reference's requirements), which is neither
 importable here nor vendored, and the reference holds no fixture of a decoded image.  The block structure below follows the 2-D originals of the
@@ -52,53 +54,60 @@ def rb(t):
     return t.to(torch.bfloat16).float()
 
 
+def shape_conv(out, name, co, ci, k):
+    out[name + ".weight"] = (co, ci, k, k)
+    out[name + ".bias"] = (co,)
+
+
+def shape_norm(out, name, c):
+    out[name + ".weight"] = (c,)
+    out[name + ".bias"] = (c,)
+
+
+def shape_resnet(out, name, ci, co):
+    shape_norm(out, name + ".norm1", ci)
+    shape_conv(out, name + ".conv1", co, ci, 3)
+    shape_norm(out, name + ".norm2", co)
+    shape_conv(out, name + ".conv2", co, co, 3)
+    if ci != co:
+        shape_conv(out, name + ".conv_shortcut", co, ci, 1)
+
+
+def shape_mid_block(out, name, c, attention):
+    shape_resnet(out, name + ".resnets.0", c, c)
+    if attention:
+        a = name + ".attentions.0"
+        shape_norm(out, a + ".group_norm", c)
+        for n in ("to_q", "to_k", "to_v", "to_out.0"):
+            out[f"{a}.{n}.weight"] = (c, c)
+            out[f"{a}.{n}.bias"] = (c,)
+    shape_resnet(out, name + ".resnets.1", c, c)
+
+
 def param_shapes(cfg: VaeConfig):
     """diffusers key -> shape for the decoder half of AutoencoderKL."""
     ch = list(reversed(cfg.block_out_channels))
     out = {}
-
-    def conv(name, co, ci, k):
-        out[name + ".weight"] = (co, ci, k, k)
-        out[name + ".bias"] = (co,)
-
-    def norm(name, c):
-        out[name + ".weight"] = (c,)
-        out[name + ".bias"] = (c,)
-
-    def resnet(name, ci, co):
-        norm(name + ".norm1", ci)
-        conv(name + ".conv1", co, ci, 3)
-        norm(name + ".norm2", co)
-        conv(name + ".conv2", co, co, 3)
-        if ci != co:
-            conv(name + ".conv_shortcut", co, ci, 1)
-
-    conv("decoder.conv_in", ch[0], cfg.latent_channels, 3)
-    resnet("decoder.mid_block.resnets.0", ch[0], ch[0])
-    if cfg.mid_block_add_attention:
-        a = "decoder.mid_block.attentions.0"
-        norm(a + ".group_norm", ch[0])
-        for n in ("to_q", "to_k", "to_v", "to_out.0"):
-            out[f"{a}.{n}.weight"] = (ch[0], ch[0])
-            out[f"{a}.{n}.bias"] = (ch[0],)
-    resnet("decoder.mid_block.resnets.1", ch[0], ch[0])
+    shape_conv(out, "decoder.conv_in", ch[0], cfg.latent_channels, 3)
+    shape_mid_block(out, "decoder.mid_block", ch[0], cfg.mid_block_add_attention)
     prev = ch[0]
     for i, co in enumerate(ch):
         for j in range(cfg.layers_per_block + 1):
-            resnet(f"decoder.up_blocks.{i}.resnets.{j}", prev if j == 0 else co, co)
+            shape_resnet(out, f"decoder.up_blocks.{i}.resnets.{j}", prev if j == 0 else co, co)
         if i != len(ch) - 1:
-            conv(f"decoder.up_blocks.{i}.upsamplers.0.conv", co, co, 3)
+            shape_conv(out, f"decoder.up_blocks.{i}.upsamplers.0.conv", co, co, 3)
         prev = co
-    norm("decoder.conv_norm_out", ch[-1])
-    conv("decoder.conv_out", cfg.out_channels, ch[-1], 3)
+    shape_norm(out, "decoder.conv_norm_out", ch[-1])
+    shape_conv(out, "decoder.conv_out", cfg.out_channels, ch[-1], 3)
     return out
 
 
-def init_params(cfg: VaeConfig, seed=0):
-    """Random bf16-valued parameters (fp32 tensors holding bf16 values) at a scale that keeps activations O(1)."""
+def draw_params(shapes, seed):
+    """Random bf16-valued parameters (fp32 tensors holding bf16 values) for a key -> shape dictionary, drawn in its order from
+    one generator, at a scale that keeps activations O(1)."""
     g = torch.Generator().manual_seed(seed)
     P = {}
-    for k, shp in param_shapes(cfg).items():
+    for k, shp in shapes.items():
         if k.endswith(".weight") and len(shp) == 1:
             P[k] = rb(1.0 + 0.1 * torch.randn(shp, generator=g))
         elif k.endswith(".bias"):
@@ -107,6 +116,10 @@ def init_params(cfg: VaeConfig, seed=0):
             fan_in = shp[1] * (shp[2] * shp[3] if len(shp) == 4 else 1)
             P[k] = rb(torch.randn(shp, generator=g) / fan_in ** 0.5)
     return P
+
+
+def init_params(cfg: VaeConfig, seed=0):
+    return draw_params(param_shapes(cfg), seed)
 
 
 def _conv(P, name, x, pad):
@@ -174,31 +187,35 @@ def blend_h(a, b, blend_extent):
     return b
 
 
-def tiled_decode(P, cfg: VaeConfig, z, decode_tile=None):
-    """autoencoder_kl_causal_3d.py:472-525 in 2-D.  Tiles are bf16 tensors (the decoder's output dtype): the blend arithmetic
-    rounds to bf16 after every product and sum, as torch does on bf16 tensors."""
-    ts, tl, ov = tile_sizes(cfg)
-    overlap_size = int(tl * (1 - ov))
-    blend_extent = int(ts * ov)
-    row_limit = ts - blend_extent
-    dec = decode_tile or (lambda t: decoder(P, cfg, t))
+def tile_walk(x, tile, stride, blend_extent, limit, run):
+    """The walk shared by `spatial_tiled_decode` (autoencoder_kl_causal_3d.py:472-525) and `spatial_tiled_encode` (:408-462)
+    in 2-D: `run` on the tiles of side `tile`, `stride` apart, of x [B, C, H, W]; its results, [B, C', h, w] made bf16 (the
+    blend arithmetic rounds to bf16 after every product and sum, as torch does on bf16 tensors), are blended over
+    `blend_extent` with the tile above and the tile to the left, cropped to `limit` and concatenated."""
     rows = []
-    for i in range(0, z.shape[-2], overlap_size):
+    for i in range(0, x.shape[-2], stride):
         row = []
-        for j in range(0, z.shape[-1], overlap_size):
-            row.append(dec(z[:, :, i:i + tl, j:j + tl]).to(torch.bfloat16))
+        for j in range(0, x.shape[-1], stride):
+            row.append(run(x[:, :, i:i + tile, j:j + tile]).to(torch.bfloat16))
         rows.append(row)
     result_rows = []
     for i, row in enumerate(rows):
         result_row = []
-        for j, tile in enumerate(row):
+        for j, t in enumerate(row):
             if i > 0:
-                tile = blend_v(rows[i - 1][j], tile, blend_extent)
+                t = blend_v(rows[i - 1][j], t, blend_extent)
             if j > 0:
-                tile = blend_h(row[j - 1], tile, blend_extent)
-            result_row.append(tile[..., :row_limit, :row_limit])
+                t = blend_h(row[j - 1], t, blend_extent)
+            result_row.append(t[..., :limit, :limit])
         result_rows.append(torch.cat(result_row, dim=-1))
     return torch.cat(result_rows, dim=-2)
+
+
+def tiled_decode(P, cfg: VaeConfig, z, decode_tile=None):
+    """autoencoder_kl_causal_3d.py:472-525 in 2-D: latent tiles, the decoder's bf16 images blended."""
+    ts, tl, ov = tile_sizes(cfg)
+    blend_extent = int(ts * ov)
+    return tile_walk(z, tl, int(tl * (1 - ov)), blend_extent, ts - blend_extent, decode_tile or (lambda t: decoder(P, cfg, t)))
 
 
 def decode(P, cfg: VaeConfig, z, use_tiling=True):

@@ -1,4 +1,6 @@
-"""Shared test helpers: fixture loading, exact-grid operands, process groups."""
+"""Shared test helpers: fixture loading, exact-grid operands, process groups, the C-ABI call recorder of the launch traces."""
+import ctypes
+import hashlib
 import json
 import os
 
@@ -153,3 +155,96 @@ def run_ranks(worker, world, timeout=300, extra=()):
             p.join(timeout=10)
             if p.is_alive():
                 p.kill()
+
+
+class Recorder:
+    """Stands in for the ctypes handle `ops.lib()` returns: forwards every call and appends [name, return value, arguments].
+    Pointers (the `c_void_p` arguments of `signatures`) are named `<buffer>+<byte offset>` after the buffer they fall into, of
+    those that `buffers()` lists as (name, address, bytes) at the time of the call -- `buffers` is None while nothing is to
+    be named -- and any other address is a temporary, `tmp<k>` with k the index of the first call that used that exact
+    address (`tmp<k>.<j>` for the further new addresses of that call)."""
+
+    def __init__(self, real, signatures):
+        self.real, self.signatures = real, signatures
+        self.buffers, self.calls, self.first_use = None, [], {}
+
+    def _pointer(self, v, bufs):
+        v = getattr(v, "value", v)
+        if not v:
+            return "null"
+        for name, lo, size in bufs:
+            if lo <= v < lo + size:
+                return f"{name}+{v - lo}"
+        if v not in self.first_use:            # (the second, third new address of one call: tmp<k>.1, tmp<k>.2)
+            self.first_use[v] = f"tmp{len(self.calls)}" + (f".{self.fresh}" if self.fresh else "")
+            self.fresh += 1
+        return self.first_use[v]
+
+    def __getattr__(self, name):
+        fn = getattr(self.real, name)
+        argtypes = self.signatures[name][1]
+
+        def call(*args):
+            bufs = self.buffers() if self.buffers is not None else []
+            self.fresh = 0
+            rec = [self._pointer(a, bufs) if t is ctypes.c_void_p else (a if isinstance(a, (int, float)) else "struct")
+                   for a, t in zip(args, argtypes)]
+            assert len(args) == len(argtypes), name
+            ret = fn(*args)
+            self.calls.append([name, ret, rec])
+            return ret
+
+        return call
+
+
+def tensor_extents(named):
+    """(name, address, bytes) of those of the (name, value) pairs that are non-empty device tensors: a Recorder's buffers."""
+    import torch
+    return [(name, t.data_ptr(), t.numel() * t.element_size()) for name, t in named
+            if isinstance(t, torch.Tensor) and t.is_cuda and t.numel()]
+
+
+def scratch_buffers(ops):
+    """ops' own caches, as the launch traces name them"""
+    return [(f"scratch.{key[0]}", t) for key, t in ops._scratch.items()] + \
+        [(f"sk_ws{i}", t) for i, t in enumerate(ops._sk_ws.values())]
+
+
+def trace_canonical(calls):
+    return "\n".join(json.dumps(c) for c in calls)
+
+
+def trace_digest(calls):
+    return dict(count=len(calls), sha256=hashlib.sha256(trace_canonical(calls).encode()).hexdigest())
+
+
+def assert_trace(name, calls, want):
+    """`calls` of pass `name` against its fixture entry: call for call where the fixture holds them, else count and sha256."""
+    calls = json.loads(json.dumps(calls))
+    if "calls" in want:
+        for i, (got, exp) in enumerate(zip(calls, want["calls"])):
+            assert got == exp, f"{name}: call {i} differs\n recorded: {exp}\n this code: {got}"
+        assert len(calls) == len(want["calls"]), \
+            f"{name}: {len(calls)} calls, recorded {len(want['calls'])}; first extra: {(calls + want['calls'])[min(len(calls), len(want['calls']))]}"
+    else:
+        assert trace_digest(calls) == want, f"{name}: {trace_digest(calls)} != recorded {want}"
+
+
+def record_traces(path, passes, run_pass):
+    """Write a launch-trace fixture: every pass of `passes` (name -> spec; spec["full"] False: count and sha256 only) through
+    `run_pass(spec, monkeypatch)`, twice, the second time in the reverse order on a used allocator, to show that the record
+    does not depend on what ran before."""
+    import pytest
+    import torch
+    first = {n: run_pass(s, pytest.MonkeyPatch()) for n, s in passes.items()}
+    junk = [torch.empty(n, device="cuda") for n in (100, 5000, 70000, 300, 1 << 20)]
+    del junk[::2]
+    again = {n: run_pass(passes[n], pytest.MonkeyPatch()) for n in reversed(list(passes))}
+    for n in passes:
+        assert trace_canonical(first[n]) == trace_canonical(again[n]), f"{n}: the record is not reproducible within one process"
+    out = {n: dict(calls=c) if passes[n].get("full", True) else trace_digest(c) for n, c in first.items()}
+    with open(path, "w") as f:
+        f.write('{"passes": {\n' + ",\n".join(
+            f'{json.dumps(n)}: ' + ('{"calls": [\n' + ",\n".join(json.dumps(c) for c in v["calls"]) + "\n]}" if "calls" in v
+                                    else json.dumps(v)) for n, v in out.items()) + "\n}}\n")
+    print({n: trace_digest(c) for n, c in first.items()}, os.path.getsize(path))

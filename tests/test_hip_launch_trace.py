@@ -3,7 +3,7 @@
 every pointer as `<buffer>+<byte offset>` -- has to be the recorded one.  A wrong N / K / row range / operand address at one
 of the description's users shows here as the first differing call instead of as a tolerance failure of a whole model.
 
-`ops.lib` is replaced by a recording proxy and nothing else is patched.  Pointers (the `c_void_p` arguments of
+`ops.lib` is replaced by a recording proxy (helpers.Recorder) and nothing else is patched.  Pointers (the `c_void_p` arguments of
 `_lib.SIGNATURES`) are named after the registered buffer they fall into -- the parameter stores, the `_Work` / `_Train` bases,
 `tr.save`, `tr.keep`, `ops._scratch`, `ops._sk_ws` -- and any other address is a temporary, `tmp<k>` with k the index of the
 first call that used that exact address (`tmp<k>.<j>` for the further new addresses of that call).  Which temporaries share
@@ -13,8 +13,6 @@ the backward on the calling thread: the record then does not depend on what ran 
 `python tests/test_hip_launch_trace.py --write` records tests/golden/launch_trace.json (on an MI355X).  The persistent-GEMM-
 only entry points need >= 128 tiles of 256 x 256 to take a problem: here they are called and refuse (return code 1 in the
 trace), the full-width tests run them."""
-import ctypes
-import hashlib
 import json
 import os
 import sys
@@ -23,7 +21,8 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from helpers import GOLDEN, make_inputs, small_cfg  # noqa: E402
+from helpers import (GOLDEN, Recorder, assert_trace, make_inputs, record_traces, scratch_buffers, small_cfg,  # noqa: E402
+                     tensor_extents)
 
 pytestmark = pytest.mark.gpu
 FIXTURE = os.path.join(GOLDEN, "launch_trace.json")
@@ -49,69 +48,19 @@ PASSES = {
 
 
 def _buffers(model, ops):
-    out = []
-
-    def add(name, t):
-        if isinstance(t, torch.Tensor) and t.is_cuda and t.numel():
-            out.append((name, t.data_ptr(), t.numel() * t.element_size()))
-
+    named = []
     for sname, st in (("store", model.store), ("lora", model.lora)):
-        for b in ("w16", "w32", "g32"):
-            add(f"{sname}.{b}", getattr(st, b, None))
+        named += [(f"{sname}.{b}", getattr(st, b, None)) for b in ("w16", "w32", "g32")]
     for wi, base in enumerate(model._work.values()):
-        for k, v in vars(base).items():
-            add(f"work{wi}.{k}", v)
+        named += [(f"work{wi}.{k}", v) for k, v in vars(base).items()]
         tr = base.train
         if tr is None:
             continue
-        for k, v in vars(tr).items():
-            add(f"train{wi}.{k}", v)
-        for k, v in tr.save.items():
-            add(f"train{wi}.save.{k}", v)
+        named += [(f"train{wi}.{k}", v) for k, v in vars(tr).items()]
+        named += [(f"train{wi}.save.{k}", v) for k, v in tr.save.items()]
         for i, kb in enumerate(tr.keep or []):
-            for k, v in kb.items():
-                add(f"train{wi}.keep{i}.{k}", v)
-    for key, t in ops._scratch.items():
-        add(f"scratch.{key[0]}", t)
-    for i, t in enumerate(ops._sk_ws.values()):
-        add(f"sk_ws{i}", t)
-    return out
-
-
-class Recorder:
-    """Stands in for the ctypes handle `ops.lib()` returns: forwards every call and appends [name, return value, arguments]."""
-
-    def __init__(self, real, signatures, ops):
-        self.real, self.signatures, self.ops = real, signatures, ops
-        self.model, self.calls, self.first_use = None, [], {}
-
-    def _pointer(self, v, bufs):
-        v = getattr(v, "value", v)
-        if not v:
-            return "null"
-        for name, lo, size in bufs:
-            if lo <= v < lo + size:
-                return f"{name}+{v - lo}"
-        if v not in self.first_use:            # (the second, third new address of one call: tmp<k>.1, tmp<k>.2)
-            self.first_use[v] = f"tmp{len(self.calls)}" + (f".{self.fresh}" if self.fresh else "")
-            self.fresh += 1
-        return self.first_use[v]
-
-    def __getattr__(self, name):
-        fn = getattr(self.real, name)
-        argtypes = self.signatures[name][1]
-
-        def call(*args):
-            bufs = _buffers(self.model, self.ops) if self.model is not None else []
-            self.fresh = 0
-            rec = [self._pointer(a, bufs) if t is ctypes.c_void_p else (a if isinstance(a, (int, float)) else "struct")
-                   for a, t in zip(args, argtypes)]
-            assert len(args) == len(argtypes), name
-            ret = fn(*args)
-            self.calls.append([name, ret, rec])
-            return ret
-
-        return call
+            named += [(f"train{wi}.keep{i}.{k}", v) for k, v in kb.items()]
+    return tensor_extents(named + scratch_buffers(ops))
 
 
 def run_pass(spec, monkeypatch):
@@ -122,7 +71,7 @@ def run_pass(spec, monkeypatch):
     keep = spec.get("keep")
     for name, v in zip(("KEEP_ACTS", "KEEP_FF", "KEEP_QKV"), keep or ()):
         monkeypatch.setattr(FB, name, v)
-    rec = Recorder(_lib.lib(), _lib.SIGNATURES, ops)
+    rec = Recorder(_lib.lib(), _lib.SIGNATURES)
     monkeypatch.setattr(ops, "lib", lambda: rec)
     ops._scratch.clear()
     ops._sk_ws.clear()
@@ -137,7 +86,7 @@ def run_pass(spec, monkeypatch):
         inputs = [t.cuda() for t in make_inputs(B, hg, wg, L, seed=3)]
         x, ehs, pooled, ids, tids, t, gd = inputs
         R = torch.randn(B, hg * wg, 64, generator=torch.Generator().manual_seed(9)).cuda()
-        rec.model = m
+        rec.buffers = lambda: _buffers(m, ops)
         del rec.calls[:]                                   # (attaching adapters merges them: not part of the pass)
         rec.first_use.clear()
         if keep is None:
@@ -150,21 +99,13 @@ def run_pass(spec, monkeypatch):
             (out.float() * R).sum().backward()
             del out
         torch.cuda.synchronize()
-        rec.model = None
+        rec.buffers = None
         del m, inputs, x, ehs, pooled, ids, tids, t, gd, R
     monkeypatch.undo()
     ops._scratch.clear()
     ops._sk_ws.clear()
     del pool
     return rec.calls
-
-
-def canonical(calls):
-    return "\n".join(json.dumps(c) for c in calls)
-
-
-def digest(calls):
-    return dict(count=len(calls), sha256=hashlib.sha256(canonical(calls).encode()).hexdigest())
 
 
 @pytest.fixture(scope="module")
@@ -175,32 +116,11 @@ def recorded():
 
 @pytest.mark.parametrize("name", list(PASSES))
 def test_launch_sequence_is_the_recorded_one(name, recorded, monkeypatch):
-    calls = json.loads(json.dumps(run_pass(PASSES[name], monkeypatch)))
-    want = recorded[name]
-    if "calls" in want:
-        for i, (got, exp) in enumerate(zip(calls, want["calls"])):
-            assert got == exp, f"{name}: call {i} differs\n recorded: {exp}\n this code: {got}"
-        assert len(calls) == len(want["calls"]), \
-            f"{name}: {len(calls)} calls, recorded {len(want['calls'])}; first extra: {(calls + want['calls'])[min(len(calls), len(want['calls']))]}"
-    else:
-        assert digest(calls) == want, f"{name}: {digest(calls)} != recorded {want}"
+    assert_trace(name, run_pass(PASSES[name], monkeypatch), recorded[name])
 
 
 if __name__ == "__main__":
-    # record the fixture; run twice, the second time in the reverse order on a used allocator, to show that the record does not
-    # depend on what ran before
+    # record the fixture (twice, the second time in the reverse order: helpers.record_traces)
     assert sys.argv[1:2] == ["--write"], "usage: python tests/test_hip_launch_trace.py --write [PATH]"
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    path = sys.argv[2] if len(sys.argv) > 2 else FIXTURE
-    first = {n: run_pass(s, pytest.MonkeyPatch()) for n, s in PASSES.items()}
-    junk = [torch.empty(n, device="cuda") for n in (100, 5000, 70000, 300, 1 << 20)]
-    del junk[::2]
-    again = {n: run_pass(PASSES[n], pytest.MonkeyPatch()) for n in reversed(list(PASSES))}
-    for n in PASSES:
-        assert canonical(first[n]) == canonical(again[n]), f"{n}: the record is not reproducible within one process"
-    out = {n: dict(calls=c) if PASSES[n].get("full", True) else digest(c) for n, c in first.items()}
-    with open(path, "w") as f:
-        f.write('{"passes": {\n' + ",\n".join(
-            f'{json.dumps(n)}: ' + ('{"calls": [\n' + ",\n".join(json.dumps(c) for c in v["calls"]) + "\n]}" if "calls" in v
-                                    else json.dumps(v)) for n, v in out.items()) + "\n}}\n")
-    print({n: digest(c) for n, c in first.items()}, os.path.getsize(path))
+    record_traces(sys.argv[2] if len(sys.argv) > 2 else FIXTURE, PASSES, run_pass)

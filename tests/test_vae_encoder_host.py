@@ -14,10 +14,11 @@ BF16 = torch.bfloat16
 
 
 def test_encoder_key_inventory_of_the_flux_vae():
-    from mixgrpo_amd.vae import VaeConfig, _decoder_keys, _encoder_keys, _encoder_shapes
+    from mixgrpo_amd.vae import VaeConfig
+    from mixgrpo_amd.vae_arch import param_shapes
     cfg = VaeConfig()
-    shp = _encoder_shapes(cfg)
-    keys = _encoder_keys(cfg)
+    shp = param_shapes(cfg, "encoder")
+    keys = list(shp)
     wb = lambda names: [f"{n}.{p}" for n in names for p in ("weight", "bias")]
     block0 = wb(["encoder.down_blocks.0.resnets.0.norm1", "encoder.down_blocks.0.resnets.0.conv1",
                  "encoder.down_blocks.0.resnets.0.norm2", "encoder.down_blocks.0.resnets.0.conv2",
@@ -44,10 +45,22 @@ def test_encoder_key_inventory_of_the_flux_vae():
     # conv_in 2; blocks 0 and 3: 2 resnets x 8 (+ 2 for block 0's downsampler); blocks 1 and 2: 8 + 10 (one shortcut) + 2;
     # mid block 8 + 10 + 8; norm_out 2; conv_out 2
     assert len(keys) == 2 + (16 + 2) + (18 + 2) + (18 + 2) + 16 + 26 + 2 + 2 == 106
-    assert len(set(keys)) == len(keys) and not set(keys) & set(_decoder_keys(cfg))
+    assert len(set(keys)) == len(keys) and not set(keys) & set(param_shapes(cfg, "decoder"))
     assert shp == ER.param_shapes(OV.VaeConfig())                                           # the helper's restatement
     n = sum(torch.Size(s).numel() for s in shp.values())
     assert 34_000_000 < n < 35_000_000                                                      # the FLUX VAE encoder: 34.2 M
+
+
+@pytest.mark.parametrize("kw", [{}, dict(block_out_channels=(64, 128, 128), layers_per_block=1),
+                                dict(block_out_channels=(64, 64), layers_per_block=1, mid_block_add_attention=False)])
+def test_both_inventories_equal_the_restatements_in_order(kw):
+    """Key by key and in order (the order `init_synthetic` draws in): the decoder's against oracle/vae.py, the encoder's
+    against tests/vae_encoder_ref.py -- neither of which reads the product's layer list."""
+    from mixgrpo_amd.vae import VaeConfig
+    from mixgrpo_amd.vae_arch import param_shapes
+    cfg, ocfg = VaeConfig(**kw), OV.VaeConfig(**kw)
+    assert list(param_shapes(cfg, "decoder").items()) == list(OV.param_shapes(ocfg).items())
+    assert list(param_shapes(cfg, "encoder").items()) == list(ER.param_shapes(ocfg).items())
 
 
 SMALL = dict(block_out_channels=(64, 64), layers_per_block=1, sample_size=32)

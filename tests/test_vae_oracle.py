@@ -65,7 +65,8 @@ def test_decode_latents_unpacks_like_the_trainer():
 # (its own `__init__` tile-size rule, `blend_v` / `blend_h`, `spatial_tiled_decode` with a recording decoder stand-in;
 # fastvideo/models/hunyuan/vae/autoencoder_kl_causal_3d.py:132-139, 384-399, 472-525).  The oracle AND the product's tiling
 # (mixgrpo_amd/vae.py: `_blend`, `AutoencoderKL.tiled_decode`, the constructor's tile sizes -- host code, runs on CPU tensors)
-# are held to them bit for bit.  The decoder's convolutions / GroupNorm / attention stay unpinned (diffusers, absent).
+# are held to them bit for bit: the tiling is pinned to the reference's vendored 3-D lineage; parity with diffusers' 2-D
+# AutoencoderKL.tiled_decode is unpinned, as are the decoder's convolutions / GroupNorm / attention (diffusers, absent).
 import json
 import os
 

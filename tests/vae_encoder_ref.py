@@ -8,7 +8,8 @@ like the decoder oracle: diffusers is not importable here.  The block order foll
 resnets then downsamplers, unet_causal_3d_blocks.py); the 2-D downsampler is diffusers' Downsample2D(padding=0), recollected:
 `F.pad(x, (0, 1, 0, 1))` then `Conv2d(3, stride=2)` (the lineage's DownsampleCausal3D, :208, pads differently).  The Gaussian is
 DiagonalGaussianDistribution (vae.py:321-353,384) as torch evaluates it on bf16 tensors; the tiling is `spatial_tiled_encode`
-(autoencoder_kl_causal_3d.py:408-470) in 2-D with the decoder oracle's `blend_v` / `blend_h` (pinned to the reference).
+(autoencoder_kl_causal_3d.py:408-470) in 2-D on the decoder oracle's tile walk and `blend_v` / `blend_h` (pinned to the
+reference's vendored 3-D lineage).
 """
 import torch
 import torch.nn.functional as F
@@ -23,57 +24,23 @@ def param_shapes(cfg):
     """diffusers key -> shape for the encoder half; block i in the forward order of `block_out_channels`."""
     ch = list(cfg.block_out_channels)
     out = {}
-
-    def conv(name, co, ci, k):
-        out[name + ".weight"] = (co, ci, k, k)
-        out[name + ".bias"] = (co,)
-
-    def norm(name, c):
-        out[name + ".weight"] = (c,)
-        out[name + ".bias"] = (c,)
-
-    def resnet(name, ci, co):
-        norm(name + ".norm1", ci)
-        conv(name + ".conv1", co, ci, 3)
-        norm(name + ".norm2", co)
-        conv(name + ".conv2", co, co, 3)
-        if ci != co:
-            conv(name + ".conv_shortcut", co, ci, 1)
-
-    conv("encoder.conv_in", ch[0], IN_CHANNELS, 3)
+    OV.shape_conv(out, "encoder.conv_in", ch[0], IN_CHANNELS, 3)
     prev = ch[0]
     for i, co in enumerate(ch):
         for j in range(cfg.layers_per_block):
-            resnet(f"encoder.down_blocks.{i}.resnets.{j}", prev if j == 0 else co, co)
+            OV.shape_resnet(out, f"encoder.down_blocks.{i}.resnets.{j}", prev if j == 0 else co, co)
         if i != len(ch) - 1:
-            conv(f"encoder.down_blocks.{i}.downsamplers.0.conv", co, co, 3)
+            OV.shape_conv(out, f"encoder.down_blocks.{i}.downsamplers.0.conv", co, co, 3)
         prev = co
-    resnet("encoder.mid_block.resnets.0", prev, prev)
-    if cfg.mid_block_add_attention:
-        a = "encoder.mid_block.attentions.0"
-        norm(a + ".group_norm", prev)
-        for n in ("to_q", "to_k", "to_v", "to_out.0"):
-            out[f"{a}.{n}.weight"] = (prev, prev)
-            out[f"{a}.{n}.bias"] = (prev,)
-    resnet("encoder.mid_block.resnets.1", prev, prev)
-    norm("encoder.conv_norm_out", prev)
-    conv("encoder.conv_out", 2 * cfg.latent_channels, prev, 3)
+    OV.shape_mid_block(out, "encoder.mid_block", prev, cfg.mid_block_add_attention)
+    OV.shape_norm(out, "encoder.conv_norm_out", prev)
+    OV.shape_conv(out, "encoder.conv_out", 2 * cfg.latent_channels, prev, 3)
     return out
 
 
 def init_params(cfg, seed=0):
     """Random bf16-valued parameters (fp32 tensors), the decoder oracle's scales."""
-    g = torch.Generator().manual_seed(seed)
-    P = {}
-    for k, shp in param_shapes(cfg).items():
-        if k.endswith(".weight") and len(shp) == 1:
-            P[k] = OV.rb(1.0 + 0.1 * torch.randn(shp, generator=g))
-        elif k.endswith(".bias"):
-            P[k] = OV.rb(0.05 * torch.randn(shp, generator=g))
-        else:
-            fan_in = shp[1] * (shp[2] * shp[3] if len(shp) == 4 else 1)
-            P[k] = OV.rb(torch.randn(shp, generator=g) / fan_in ** 0.5)
-    return P
+    return OV.draw_params(param_shapes(cfg), seed)
 
 
 def downsample(P, name, x):
@@ -114,29 +81,10 @@ def gaussian(moments, noise=None):
 
 
 def tiled_moments(P, cfg, x, encode_tile=None):
-    """autoencoder_kl_causal_3d.py:408-462 in 2-D: tiles are bf16 tensors, blended in place on the later tile."""
+    """autoencoder_kl_causal_3d.py:408-462 in 2-D: image tiles, their bf16 moments blended in place on the later tile."""
     ts, tl, ov = OV.tile_sizes(cfg)
-    overlap_size = int(ts * (1 - ov))
     blend_extent = int(tl * ov)
-    row_limit = tl - blend_extent
-    enc = encode_tile or (lambda t: encoder(P, cfg, t))
-    rows = []
-    for i in range(0, x.shape[-2], overlap_size):
-        row = []
-        for j in range(0, x.shape[-1], overlap_size):
-            row.append(enc(x[:, :, i:i + ts, j:j + ts]).to(BF16))
-        rows.append(row)
-    result_rows = []
-    for i, row in enumerate(rows):
-        result_row = []
-        for j, tile in enumerate(row):
-            if i > 0:
-                tile = OV.blend_v(rows[i - 1][j], tile, blend_extent)
-            if j > 0:
-                tile = OV.blend_h(row[j - 1], tile, blend_extent)
-            result_row.append(tile[..., :row_limit, :row_limit])
-        result_rows.append(torch.cat(result_row, dim=-1))
-    return torch.cat(result_rows, dim=-2)
+    return OV.tile_walk(x, ts, int(ts * (1 - ov)), blend_extent, tl - blend_extent, encode_tile or (lambda t: encoder(P, cfg, t)))
 
 
 def encode_moments(P, cfg, x, use_tiling=False):
