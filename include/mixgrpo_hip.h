@@ -475,6 +475,56 @@ int mgx_lora_wgrad(const uint16_t* small, const uint16_t* big, float* G, float* 
  * rounding to bf16 (an fp32 sum misses bf16(exact) by several ulps where W0 and s B A cancel). */
 int mgx_lora_merge(const float* W0, const float* Bt, const float* A, uint16_t* W16, int N, int K, int r, float s, void* stream);
 
+/* ---- CLIP ViT image tower (csrc/clip.hip): the network behind the reference's HPSClipRewardModel, PickScoreRewardModel and
+ * CLIPScoreRewardModel (fastvideo/models/reward_model/{hps_score,pick_score,clip_score}.py), inference only.  Its Linears are
+ * mgx_gemm_bf16 launches; these entry points are what sits between them.
+ *
+ * Decoded image -> normalised patch rows: what `self.img_processor(image)` (hps_score.py:68), `self.processor(images=[image])`
+ * (pick_score.py:55-61) and `self.preprocess(image)` (clip_score.py:57) do on a PIL image on the host.
+ *   image [3][H][W] bf16 in about [-1, 1] (AutoencoderKL.decode's output);
+ *   1. levels 0..255 as VaeImageProcessor.postprocess gives them under bf16: bf16(bf16(x / 2) + 0.5) clamped to [0, 1], times 255
+ *      in fp32, rounded half to even;
+ *   2. antialiased bicubic resize (PIL's BICUBIC: Keys a = -1/2, support 2 max(in / out, 1)) of the shortest edge to R, the long
+ *      edge to floor(R long / short); horizontal then vertical pass with no rounding in between (PIL rounds to uint8 there),
+ *      weights in fp64, the intermediate image in fp32; rounded to the nearest level and clamped to 0..255;
+ *   3. centre crop R x R (top / left = floor of half the excess);  4. bf16((q / 255 - mean[c]) / std[c]), evaluated in fp32;
+ *   5. patches[py (R / p) + px][c p p + dy p + dx], Kp >= 3 p p columns per row, the columns from 3 p p on written as zero.
+ * mean, std: three floats each in HOST memory.  levels (optional, device): receives the R x R levels [3][R][R] as bytes.
+ * workspace: fp32, mgx_clip_preprocess_workspace(H, W, R) elements (-1 for sizes below 1).  H, W >= 1, R % p == 0. */
+long mgx_clip_preprocess_workspace(int H, int W, int R);
+int mgx_clip_preprocess(const uint16_t* image, int H, int W, int R, int p, const float* mean, const float* std,
+                        uint16_t* patches, int Kp, uint8_t* levels, float* workspace, long workspace_elems, void* stream);
+/* x[b][0] = bf16(cls + pos[0]), x[b][1 + i] = bf16(patch_out[b][i] + pos[1 + i]): the class token, the patch embeddings
+ * [B (S - 1)][width] bf16 and the position embeddings [S][width] (cls, pos fp32) -- CLIPVisionEmbeddings.forward / open_clip's
+ * VisionTransformer.forward up to ln_pre, inside `self.reward_model(image, text)` (hps_score.py:71). */
+int mgx_vit_embed(const uint16_t* patch_out, const float* cls, const float* pos, uint16_t* x, int B, int S, int width,
+                  void* stream);
+/* y[m][0..D) = bf16(LayerNorm(x[m][0..D); eps) * gamma + beta), rows ldx / ldy elements apart (y may be x): the nn.LayerNorm
+ * layers of the tower (ln_pre, ln_1, ln_2, ln_post; same call sites).  fp32 statistics, the variance from centred values;
+ * gamma, beta fp32 [D].  D % 64 == 0, D <= 2048. */
+int mgx_layer_norm_affine(const uint16_t* x, long ldx, const float* gamma, const float* beta, uint16_t* y, long ldy, long M, int D,
+                          float eps, void* stream);
+/* Non-causal multi-head attention of the tower's nn.MultiheadAttention / CLIPAttention (same call sites), straight from the
+ * packed projection: row b S + s of qkv [B S][ld_qkv] holds q | k | v, head h in the columns h d, width + h d and 2 width + h d
+ * (width = H d); O[b S + s][h d ..] = bf16(softmax(scale q k^T) v), ldo elements between rows.  bf16 MFMA, fp32 scores and
+ * accumulation, one rounding of O; no lse.  d % 16 == 0, d <= 128; any S >= 1, tail queries and keys masked in the kernel:
+ * nothing outside the rows [0, B S) and the head columns is read or written.  ld_qkv % 8 == 0, ldo % 4 == 0, both pointers
+ * 16-byte aligned.  Returns 1 -- nothing launched -- for S > 4096. */
+int mgx_vit_attn_fwd(const uint16_t* qkv, long ld_qkv, uint16_t* O, long ldo, int B, int H, int S, int d, float scale,
+                     void* stream);
+/* y[m][0..N) = bf16(act(x[m][0..N))), y may be x.  act 0: exact GELU x Phi(x) (nn.GELU(): open_clip ViT-H, HF hidden_act "gelu"),
+ * act 1: QuickGELU x sigmoid(1.702 x) (OpenAI weights) -- the tower's MLP activation (same call sites); mgx_gemm_bf16's GELU
+ * epilogue is the tanh form, which these networks do not use. */
+int mgx_act_rows(const uint16_t* x, long ldx, uint16_t* y, long ldy, long M, int N, int act, void* stream);
+/* out[b][0..n) (fp32) = f[b] / |f[b]|, f bf16: `image_embs / torch.norm(image_embs, dim=-1, keepdim=True)` (pick_score.py:75),
+ * F.normalize (clip_score.py:65). */
+int mgx_l2_normalize_rows(const uint16_t* f, long ldf, float* out, int B, int n, void* stream);
+/* out[b] = (logit_scale <f[b], t[b]> / (|f[b]| |t[b]|) - mean) / std, fp32 sums; f and t rows of bf16 or fp32 (`*_is_f32`), ldt
+ * may be 0 (one text row for every image).  The score of pick_score.py:73-82 (logit_scale = exp(model.logit_scale)), and with
+ * logit_scale 1, mean 0, std 1 the cosine of hps_score.py:70-77 and clip_score.py:63-70. */
+int mgx_cosine_score(const void* f, int f_is_f32, long ldf, const void* t, int t_is_f32, long ldt, float* out, int B, int n,
+                     float logit_scale, float mean, float std, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

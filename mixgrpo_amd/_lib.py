@@ -116,6 +116,14 @@ SIGNATURES = {
     "mgx_lora_wgrad_workspace": (_L, [_L, _I, _I]),
     "mgx_lora_wgrad": (_I, [_P, _P, _P, _P, _L, _L, _I, _I, _L, _L, _L, _F, _P]),
     "mgx_lora_merge": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "mgx_clip_preprocess_workspace": (_L, [_I, _I, _I]),
+    "mgx_clip_preprocess": (_I, [_P, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _I, _P, _P, _L, _P]),
+    "mgx_vit_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "mgx_layer_norm_affine": (_I, [_P, _L, _P, _P, _P, _L, _L, _I, _F, _P]),
+    "mgx_vit_attn_fwd": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _F, _P]),
+    "mgx_act_rows": (_I, [_P, _L, _P, _L, _L, _I, _I, _P]),
+    "mgx_l2_normalize_rows": (_I, [_P, _L, _P, _I, _I, _P]),
+    "mgx_cosine_score": (_I, [_P, _I, _L, _P, _I, _L, _P, _I, _I, _F, _F, _F, _P]),
 }
 
 _lib = None

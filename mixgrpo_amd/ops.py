@@ -28,11 +28,14 @@ class Rows:
         return Rows(t, t.numel() // cols, cols)
 
 
-def gemm(A: Rows, W, bias, C: Rows, N, K, epi=EPI_BIAS, gate=None, gate_ld=0, aux=None, beta=0.0, ldw=None, ldaux=None):
+def gemm(A: Rows, W, bias, C: Rows, N, K, epi=EPI_BIAS, gate=None, gate_ld=0, aux=None, beta=0.0, ldw=None, ldaux=None,
+         stream_k=None):
     """C = epi(A @ W[N,K]^T + bias).  `aux`: plain [M, ldaux] matrix (ldaux defaults to N); pass a tensor whose
-    data_ptr() is its first element."""
+    data_ptr() is its first element.  `stream_k`: None = the module's GEMM_STREAM_K; False = no stream-K workspace, every tile
+    computed whole, so a row's result does not depend on how many rows the call has."""
     assert A.M == C.M
-    _profiled(_gemm_launch, (A, W, bias, C, N, K, epi, gate, gate_ld, aux, beta, ldw, ldaux), 2.0 * A.M * N * K, (A.M, N, K, epi))
+    _profiled(_gemm_launch, (A, W, bias, C, N, K, epi, gate, gate_ld, aux, beta, ldw, ldaux, stream_k), 2.0 * A.M * N * K,
+              (A.M, N, K, epi))
 
 
 GEMM_PROFILE = None
@@ -79,8 +82,8 @@ def linear_t(X, W, bias, Ct, tokens, F, K, ld_ct, tok_rpb, ct_bstride):
                      2.0 * tokens * F * K, (F, tokens, K, EPI_BIAS))
 
 
-def _gemm_launch(A, W, bias, C, N, K, epi, gate, gate_ld, aux, beta, ldw, ldaux):
-    ws = _sk_workspace(C.t.device) if GEMM_STREAM_K else None
+def _gemm_launch(A, W, bias, C, N, K, epi, gate, gate_ld, aux, beta, ldw, ldaux, stream_k=None):
+    ws = _sk_workspace(C.t.device) if (GEMM_STREAM_K if stream_k is None else stream_k) else None
     check(lib().mgx_gemm_bf16_sk(ptr(A.t), ptr(W), ptr(bias), ptr(C.t), None if gate is None else gate.data_ptr(),
                                  None if aux is None else aux.data_ptr(), (N if ldaux is None else ldaux), A.M, N, K, A.ld,
                                  A.rpb, A.bstride, K if ldw is None else ldw, C.ld, C.rpb, C.bstride, gate_ld, epi, beta,
@@ -444,3 +447,58 @@ def diag_gaussian(moments, ld, noise, mean, std, sample, Cz, H, W):
 
 def softmax_rows(S, P, M, n, scale):
     check(lib().mgx_softmax_rows_f32(ptr(S), S.stride(0), ptr(P), P.stride(0), M, n, scale, stream()))
+
+
+# ------------------------------------------------------------------------------------------------ CLIP ViT tower (csrc/clip.hip)
+ACT_GELU, ACT_QUICK_GELU = 0, 1
+
+
+def clip_patch_cols(patch):
+    """Columns of a patch row: 3 p p rounded up to the GEMM's K % 64 == 0 (588 -> 640)."""
+    return (3 * patch * patch + 63) // 64 * 64
+
+
+def clip_preprocess(image, R, patch, mean, std, patches, levels=None):
+    """image [3, H, W] bf16 in about [-1, 1] -> patches [(R / p)^2, clip_patch_cols(p)] bf16 (`mgx_clip_preprocess`); `levels`:
+    optional uint8 [3, R, R] that receives the resized, cropped 0..255 image."""
+    import ctypes
+    _, H, W = image.shape
+    ws = scratch("clip_preprocess", lib().mgx_clip_preprocess_workspace(H, W, R), F32, image.device)
+    f3 = ctypes.c_float * 3
+    check(lib().mgx_clip_preprocess(ptr(image), H, W, R, patch, f3(*mean), f3(*std), ptr(patches), patches.shape[-1], ptr(levels),
+                                    ptr(ws), ws.numel(), stream()))
+
+
+def vit_embed(patch_out, cls, pos, x, B, S, width):
+    check(lib().mgx_vit_embed(ptr(patch_out), ptr(cls), ptr(pos), ptr(x), B, S, width, stream()))
+
+
+def layer_norm_affine(x, ldx, gamma, beta, y, ldy, M, D, eps):
+    """y[m, :D] = bf16(LN(x[m, :D]; eps) * gamma + beta); x, y: tensors whose data_ptr() is the first element, rows ldx / ldy
+    elements apart (y may be x)."""
+    check(lib().mgx_layer_norm_affine(x.data_ptr(), ldx, ptr(gamma), ptr(beta), y.data_ptr(), ldy, M, D, float(eps), stream()))
+
+
+def vit_attn_fwd(qkv, ld_qkv, O, ldo, B, H, S, d, scale):
+    """O[b S + s, h d:] = softmax(scale q k^T) v from the packed projection rows q | k | v (`mgx_vit_attn_fwd`); qkv, O: tensors
+    whose data_ptr() is the first element.  False -- nothing launched -- for S > 4096."""
+    return _try(lib().mgx_vit_attn_fwd, qkv.data_ptr(), ld_qkv, O.data_ptr(), ldo, B, H, S, d, float(scale), stream())
+
+
+def act_rows(x, ldx, y, ldy, M, N, act):
+    check(lib().mgx_act_rows(x.data_ptr(), ldx, y.data_ptr(), ldy, M, N, act, stream()))
+
+
+def l2_normalize_rows(f, out):
+    check(lib().mgx_l2_normalize_rows(ptr(f), f.stride(0), ptr(out), f.shape[0], f.shape[1], stream()))
+
+
+def cosine_score(f, t, out, logit_scale=1.0, mean=0.0, std=1.0):
+    """out[b] = (logit_scale cos(f[b], t[b]) - mean) / std; f [B, n], t [B, n] or [1, n], bf16 or fp32 rows."""
+    for a in (f, t):
+        if a.dtype not in (BF16, F32):
+            raise ValueError("cosine_score takes bf16 or fp32 rows")
+    B, n = f.shape
+    check(lib().mgx_cosine_score(ptr(f), int(f.dtype == F32), f.stride(0), ptr(t), int(t.dtype == F32),
+                                 0 if t.shape[0] == 1 else t.stride(0), ptr(out), B, n,
+                                 float(logit_scale), float(mean), float(std), stream()))

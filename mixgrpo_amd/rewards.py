@@ -1,0 +1,154 @@
+"""The reference's three CLIP rewards on the HIP image tower (mixgrpo_amd/clip_vision.py):
+
+    kind                    score                                       reference
+    HPSClipRewardModel      cosine(image, text)                         hps_score.py:70-77 (normalised features, no logit scale)
+    CLIPScoreRewardModel    cosine(image, text)                         clip_score.py:63-70
+    PickScoreRewardModel    (exp(logit_scale) * cosine - mean) / std    pick_score.py:73-82
+
+(files under fastvideo/models/reward_model/).  A prompt's text feature is constant, so -- like the T5 / CLIP prompt embeddings
+of latent_flux_rl_datasets -- it is computed once, offline, with whatever text tower the user owns (`build_text_feature_cache`)
+and looked up by prompt here (`TextFeatureCache`); the text tower and its tokenizer are not part of this package.  Only the
+image tower runs in the training loop: `decode -> ClipReward` stays on the device, with no PIL image and no host copy of one.
+
+`builtin_rewards` is a factory for `--mgx_reward_plugin mixgrpo_amd.rewards:builtin_rewards`."""
+import json
+import os
+
+import torch
+
+from . import ops
+
+KINDS = ("HPSClipRewardModel", "CLIPScoreRewardModel", "PickScoreRewardModel")
+CONFIG_ENV = "MGX_REWARD_CONFIG"
+
+
+def build_text_feature_cache(prompts, encode_text, path, batch_size=64):
+    """Write the cache `TextFeatureCache` reads: `encode_text(list of prompts) -> [n, embed]` tensor (any text tower), one row
+    per distinct prompt.  `path` ends in .safetensors (the prompts go into the file's metadata as a JSON list) or .pt (a dict
+    with `features` and `prompts`)."""
+    prompts = list(dict.fromkeys(prompts))
+    rows = [torch.as_tensor(encode_text(prompts[i:i + batch_size])).detach().float().cpu() for i in range(0, len(prompts), batch_size)]
+    feats = torch.cat(rows).contiguous()
+    if feats.dim() != 2 or feats.shape[0] != len(prompts):
+        raise ValueError(f"encode_text returned {tuple(feats.shape)} for {len(prompts)} prompts")
+    if str(path).endswith(".safetensors"):
+        from safetensors.torch import save_file
+        save_file({"features": feats}, str(path), metadata={"prompts": json.dumps(prompts)})
+    else:
+        torch.save({"features": feats, "prompts": prompts}, str(path))
+    return path
+
+
+class TextFeatureCache:
+    """features [n, embed] + the JSON list of their n prompts, from a .safetensors file (prompts in its metadata, or in a
+    `<path>.json` next to it) or a .pt file (dict with `features` and `prompts`)."""
+
+    def __init__(self, path=None, features=None, prompts=None):
+        if path is not None:
+            features, prompts = self._read(str(path))
+        self.features = torch.as_tensor(features).float()
+        self.prompts = list(prompts)
+        if self.features.dim() != 2 or self.features.shape[0] != len(self.prompts):
+            raise ValueError(f"{tuple(self.features.shape)} features for {len(self.prompts)} prompts")
+        self.index = {p: i for i, p in enumerate(self.prompts)}
+        self._on = {}
+
+    @staticmethod
+    def _read(path):
+        prompts = None
+        if path.endswith(".safetensors"):
+            from safetensors import safe_open
+            with safe_open(path, "pt") as f:
+                features = f.get_tensor("features")
+                meta = f.metadata() or {}
+            if "prompts" in meta:
+                prompts = json.loads(meta["prompts"])
+        else:
+            d = torch.load(path, map_location="cpu")
+            features, prompts = d["features"], d.get("prompts")
+        if prompts is None:
+            with open(path + ".json") as f:
+                prompts = json.load(f)
+        return features, prompts
+
+    def rows(self, prompts):
+        """Indices of the prompts; an unknown one is a KeyError that quotes it."""
+        out = []
+        for p in prompts:
+            if p not in self.index:
+                raise KeyError(f"no cached text feature for the prompt {p!r}: add it with build_text_feature_cache")
+            out.append(self.index[p])
+        return out
+
+    def lookup(self, prompts, device):
+        """[len(prompts), embed] fp32 on `device`"""
+        idx = self.rows(prompts)
+        device = torch.device(device)
+        t = self._on.get(device)
+        if t is None:
+            t = self._on[device] = self.features.to(device)
+        return t[torch.tensor(idx, device=device)].contiguous()
+
+
+class ClipReward:
+    """`(images, prompts) -> list[float]`, the order reward_adapter.compute_reward uses.  Images are [3, H, W] device tensors as
+    AutoencoderKL.decode returns them (PIL images are converted on the host); `text_features` a TextFeatureCache."""
+
+    def __init__(self, tower, text_features, kind, mean=18.0, std=8.0):
+        if kind not in KINDS:
+            raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+        if kind == "PickScoreRewardModel" and tower.logit_scale is None:
+            raise ValueError("PickScoreRewardModel needs the checkpoint's logit_scale, which this tower's state dict did not hold")
+        self.tower, self.text_features, self.kind = tower, text_features, kind
+        self.mean, self.std = float(mean), float(std)
+
+    def score_params(self):
+        """(logit scale, mean, std) of `(scale * cosine - mean) / std`"""
+        if self.kind == "PickScoreRewardModel":
+            return float(torch.tensor(self.tower.logit_scale).exp()), self.mean, self.std
+        return 1.0, 0.0, 1.0
+
+    @torch.no_grad()
+    def __call__(self, images, prompts):
+        if isinstance(prompts, str):
+            prompts = [prompts]
+        if torch.is_tensor(images):
+            images = list(images) if images.dim() == 4 else [images]
+        elif not isinstance(images, (list, tuple)):
+            images = [images]
+        if len(images) != len(prompts):
+            raise ValueError(f"{len(images)} images for {len(prompts)} prompts")
+        dev = self.tower.device
+        text = self.text_features.lookup(prompts, dev)          # before anything is launched: an unknown prompt is a KeyError
+        feats = self.tower.encode_image(images, normalize=False)
+        out = torch.empty(len(images), dtype=torch.float32, device=dev)
+        ops.cosine_score(feats, text, out, *self.score_params())
+        return out.tolist()
+
+
+def builtin_rewards(args=None):
+    """`--mgx_reward_plugin mixgrpo_amd.rewards:builtin_rewards`: reads the JSON file named by the environment variable
+    MGX_REWARD_CONFIG, `{RewardClassName: {"tower_dir": ..., "text_features": ..., ["mean": 18.0, "std": 8.0, "device": "cuda"]}}`,
+    and returns `{RewardClassName: ClipReward}`.  Rewards that name the same tower directory share one tower."""
+    from .clip_vision import ClipVisionTower
+    path = os.environ.get(CONFIG_ENV)
+    if not path:
+        raise ValueError(f"builtin_rewards: set {CONFIG_ENV} to a JSON file {{RewardClassName: {{tower_dir, text_features}}}}")
+    with open(path) as f:
+        cfg = json.load(f)
+    if not isinstance(cfg, dict) or not cfg:
+        raise ValueError(f"{path}: expected a non-empty JSON object")
+    towers, caches, out = {}, {}, {}
+    for name, c in cfg.items():
+        if name not in KINDS:
+            raise ValueError(f"{path}: {name!r} is not one of {KINDS}")
+        missing = [k for k in ("tower_dir", "text_features") if k not in c]
+        if missing:
+            raise ValueError(f"{path}: {name} lacks {missing}")
+        tkey = (c["tower_dir"], c.get("device", "cuda"))
+        if tkey not in towers:
+            towers[tkey] = ClipVisionTower.from_pretrained(*tkey)
+        if c["text_features"] not in caches:
+            caches[c["text_features"]] = TextFeatureCache(c["text_features"])
+        out[name] = ClipReward(towers[tkey], caches[c["text_features"]], name, c.get("mean", 18.0), c.get("std", 8.0))
+    return out

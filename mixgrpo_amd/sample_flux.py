@@ -56,6 +56,18 @@ def img2img_start(num_inference_steps, strength):
     return t_start
 
 
+def denormalize(image):
+    """VaeImageProcessor.postprocess's first step on the decoder's bf16 output: `(x / 2 + 0.5).clamp(0, 1)` IN THAT DTYPE, then
+    `.float()`."""
+    return (image / 2 + 0.5).clamp(0, 1).float()
+
+
+def image_levels(image):
+    """The 0..255 grid of the "pil" output: `(denormalize(x) * 255).round()` in fp32 (half to even), as a float tensor.  The one
+    statement of this rule: csrc/clip.hip's `image_level` is its kernel form, held to it by tests/test_hip_clip.py."""
+    return (denormalize(image) * 255).round()
+
+
 class DualFluxSampler:
     """`transformer`: base model, `transformer_new`: tuned model (both mixgrpo_amd.flux.FluxTransformer2DModel)."""
 
@@ -174,7 +186,8 @@ class DualFluxSampler:
         z = unpack_latents(latents, height, width, 8)
         z = (z / cfg.scaling_factor) + cfg.shift_factor
         image = self.vae.decode(z, return_dict=False)[0]
-        image = (image / 2 + 0.5).clamp(0, 1).float()
+        levels = image_levels(image) if output_type == "pil" else None
+        image = denormalize(image)
         if output_type == "pt":
             return image
         arr = image.permute(0, 2, 3, 1).cpu().numpy()
@@ -182,5 +195,5 @@ class DualFluxSampler:
             return arr
         if output_type == "pil":
             from PIL import Image
-            return [Image.fromarray((a * 255).round().astype("uint8")) for a in arr]
+            return [Image.fromarray(a) for a in levels.permute(0, 2, 3, 1).cpu().numpy().astype("uint8")]
         raise ValueError(f"unknown output_type {output_type}")
