@@ -525,6 +525,40 @@ int mgx_l2_normalize_rows(const uint16_t* f, long ldf, float* out, int B, int n,
 int mgx_cosine_score(const void* f, int f_is_f32, long ldf, const void* t, int t_is_f32, long ldt, float* out, int B, int n,
                      float logit_scale, float mean, float std, void* stream);
 
+/* ---- Text encoders (csrc/text.hip): the CLIP text tower inside `self.reward_model(image, text)` (hps_score.py:69-72),
+ * `self.model.get_text_features` (pick_score.py:64-77) and `encode_text` (clip_score.py), and the T5-XXL + CLIP-L prompt
+ * encoders behind `pipe.encode_prompt` (fastvideo/data_preprocess/preprocess_flux_embedding.py:89).  Inference only; the Linears
+ * are mgx_gemm_bf16 launches.
+ *
+ * mgx_vit_attn_fwd's contract and kernel body (packed q | k | v rows, bf16 MFMA, fp32 scores and sums, one rounding of O,
+ * nothing read or written outside the rows and the head columns, d % 16 == 0, d <= 128, returns 1 for S > 4096), plus:
+ *   causal != 0: key k contributes to query q only if k <= q (CLIPTextTransformer's causal mask / open_clip's attn_mask); key
+ *                blocks wholly above a workgroup's last query are neither loaded nor multiplied;
+ *   rel_bias (device fp32 [H][2 S - 1], or NULL): rel_bias[h][k - q + S - 1] is added to scale * q.k in fp32 before the maximum
+ *                is taken -- T5Attention's position_bias, which depends on (h, k - q) only, as a compact table.
+ * T5 calls it with scale 1, causal 0 and a table, CLIP text with scale d^-0.5, causal 1 and NULL.  With causal 0 and NULL the
+ * result equals mgx_vit_attn_fwd's bit for bit. */
+int mgx_text_attn_fwd(const uint16_t* qkv, long ld_qkv, uint16_t* O, long ldo, int B, int H, int S, int d, float scale, int causal,
+                      const float* rel_bias, void* stream);
+/* T5LayerNorm (transformers modeling_t5.py, every layer_norm / final_layer_norm under `pipe.encode_prompt`):
+ * y[m][0..D) = bf16(x * rsqrt(mean(x^2) + eps) * gamma), no mean subtraction, no bias; fp32 statistics, gamma fp32 [D], ONE
+ * rounding.  STATED DEVIATION: transformers under bf16 rounds twice, once after the normalisation (the cast back to the
+ * weight's dtype) and once after the weight.  D % 64 == 0, D <= 4096; rows ldx / ldy elements apart, y may be x. */
+int mgx_rms_norm_affine(const uint16_t* x, long ldx, const float* gamma, uint16_t* y, long ldy, long M, int D, float eps,
+                        void* stream);
+/* y[m][0..N) = bf16(act(a[m][0..N)) * b[m][0..N)), y may be a: T5DenseGatedActDense's `self.act(self.wi_0(x)) * self.wi_1(x)`
+ * (same call site); a and b are the two column halves of the fused wi_0 | wi_1 GEMM's output.  act 0, 1: as mgx_act_rows;
+ * act 2: the tanh GELU 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) -- `gelu_new`, what feed_forward_proj "gated-gelu"
+ * resolves to -- evaluated through exp(-2 |u|), which neither cancels for negative x nor overflows. */
+int mgx_gated_act_rows(const uint16_t* a, long lda, const uint16_t* b, long ldb, uint16_t* y, long ldy, long M, int N, int act,
+                       void* stream);
+/* x[m][0..D) = bf16(table[ids[m]] + pos[m % S]): nn.Embedding of the token ids plus the position embeddings
+ * (CLIPTextEmbeddings.forward; T5Stack's embed_tokens with pos == NULL; same call sites).  ids int32 [M] on the device, table
+ * bf16 [V][D], pos fp32 [S][D] or NULL.  Contract: 0 <= ids[m] < V (the Python wrapper checks it on the host before the copy;
+ * the kernel reads row 0 for an id outside, never memory outside the table). */
+int mgx_token_embed(const int* ids, const uint16_t* table, const float* pos, uint16_t* x, long M, int S, int D, int V,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,10 @@ SIGNATURES = {
     "mgx_act_rows": (_I, [_P, _L, _P, _L, _L, _I, _I, _P]),
     "mgx_l2_normalize_rows": (_I, [_P, _L, _P, _I, _I, _P]),
     "mgx_cosine_score": (_I, [_P, _I, _L, _P, _I, _L, _P, _I, _I, _F, _F, _F, _P]),
+    "mgx_text_attn_fwd": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P, _P]),
+    "mgx_rms_norm_affine": (_I, [_P, _L, _P, _P, _L, _L, _I, _F, _P]),
+    "mgx_gated_act_rows": (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P]),
+    "mgx_token_embed": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -502,3 +502,45 @@ def cosine_score(f, t, out, logit_scale=1.0, mean=0.0, std=1.0):
     check(lib().mgx_cosine_score(ptr(f), int(f.dtype == F32), f.stride(0), ptr(t), int(t.dtype == F32),
                                  0 if t.shape[0] == 1 else t.stride(0), ptr(out), B, n,
                                  float(logit_scale), float(mean), float(std), stream()))
+
+
+# ------------------------------------------------------------------------------------------------ text encoders (csrc/text.hip)
+ACT_GELU_TANH = 2
+
+
+def text_attn_fwd(qkv, ld_qkv, O, ldo, B, H, S, d, scale, causal=False, rel_bias=None):
+    """`vit_attn_fwd` with a causal mask and / or a relative-position bias table [H, 2 S - 1] fp32 (`mgx_text_attn_fwd`).
+    False -- nothing launched -- for S > 4096."""
+    if rel_bias is not None and (rel_bias.dtype != F32 or tuple(rel_bias.shape) != (H, 2 * S - 1)):
+        raise ValueError(f"rel_bias must be fp32 [{H}, {2 * S - 1}], not {rel_bias.dtype} {tuple(rel_bias.shape)}")
+    return _try(lib().mgx_text_attn_fwd, qkv.data_ptr(), ld_qkv, O.data_ptr(), ldo, B, H, S, d, float(scale), int(bool(causal)),
+                ptr(rel_bias), stream())
+
+
+def rms_norm_affine(x, ldx, gamma, y, ldy, M, D, eps):
+    """y[m, :D] = bf16(x[m, :D] * rsqrt(mean(x^2) + eps) * gamma); x, y: tensors whose data_ptr() is the first element, rows
+    ldx / ldy elements apart (y may be x)."""
+    check(lib().mgx_rms_norm_affine(x.data_ptr(), ldx, ptr(gamma), y.data_ptr(), ldy, M, D, float(eps), stream()))
+
+
+def gated_act_rows(a, lda, b, ldb, y, ldy, M, N, act):
+    """y = bf16(act(a) * b) on rows lda / ldb / ldy elements apart (y may be a); act: ACT_GELU, ACT_QUICK_GELU, ACT_GELU_TANH"""
+    check(lib().mgx_gated_act_rows(a.data_ptr(), lda, b.data_ptr(), ldb, y.data_ptr(), ldy, M, N, act, stream()))
+
+
+def token_embed(input_ids, table, pos, x):
+    """x[b S + s] = bf16(table[input_ids[b, s]] + pos[s]) (`mgx_token_embed`); `input_ids` an integer tensor [B, S], normally on
+    the host: the ids are checked where they are, before the copy to the device, and an id outside [0, V) raises a ValueError
+    that names it and its position -- nothing is launched.  pos fp32 [>= S, D] or None."""
+    if input_ids.dim() != 2 or input_ids.dtype in (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.bool):
+        raise ValueError(f"input_ids must be an integer tensor [B, S], not {input_ids.dtype} {tuple(input_ids.shape)}")
+    B, S = input_ids.shape
+    V, D = table.shape
+    bad = ((input_ids < 0) | (input_ids >= V)).nonzero()
+    if bad.numel():
+        b, s = (int(v) for v in bad[0])
+        raise ValueError(f"token id {int(input_ids[b, s])} at position ({b}, {s}) is outside the vocabulary [0, {V})")
+    if pos is not None and (pos.shape[0] < S or pos.shape[1] != D):
+        raise ValueError(f"{S} positions of width {D} need pos [>= {S}, {D}], not {tuple(pos.shape)}")
+    ids = input_ids.to(device=table.device, dtype=torch.int32).contiguous()
+    check(lib().mgx_token_embed(ptr(ids), ptr(table), ptr(pos), ptr(x), B * S, S, D, V, stream()))

@@ -5,10 +5,15 @@
     CLIPScoreRewardModel    cosine(image, text)                         clip_score.py:63-70
     PickScoreRewardModel    (exp(logit_scale) * cosine - mean) / std    pick_score.py:73-82
 
-(files under fastvideo/models/reward_model/).  A prompt's text feature is constant, so -- like the T5 / CLIP prompt embeddings
-of latent_flux_rl_datasets -- it is computed once, offline, with whatever text tower the user owns (`build_text_feature_cache`)
-and looked up by prompt here (`TextFeatureCache`); the text tower and its tokenizer are not part of this package.  Only the
-image tower runs in the training loop: `decode -> ClipReward` stays on the device, with no PIL image and no host copy of one.
+(files under fastvideo/models/reward_model/).  A prompt's text feature is constant.  It comes from one of two objects with the
+same `lookup(prompts, device)`:
+    TextTowerFeatures   encodes a prompt the first time it is seen, on the HIP text tower (mixgrpo_amd/clip_text.py) with a
+                        delegated tokenizer, and memoises it: no offline step, as the reference's models, which take
+                        `(images, prompts)` and encode the prompt themselves (hps_score.py:69-72, pick_score.py:64-77);
+    TextFeatureCache    looks it up in a file computed once, offline, with whatever text tower the user owns
+                        (`build_text_feature_cache`); an unknown prompt is a KeyError.
+Only the image tower runs on every step of the training loop: `decode -> ClipReward` stays on the device, with no PIL image and
+no host copy of one.
 
 `builtin_rewards` is a factory for `--mgx_reward_plugin mixgrpo_amd.rewards:builtin_rewards`."""
 import json
@@ -90,9 +95,34 @@ class TextFeatureCache:
         return t[torch.tensor(idx, device=device)].contiguous()
 
 
+class TextTowerFeatures:
+    """`TextFeatureCache`'s `lookup` on a text tower: `text_tower.encode_text(input_ids) -> [n, embed]` (a ClipTextTower) and
+    `tokenizer`, a callable `prompts -> int tensor [n, S]` or a tokenizer directory (text_encoders.load_tokenizer).  The unseen
+    prompts of a lookup are encoded as one batch and memoised by prompt."""
+
+    def __init__(self, text_tower, tokenizer):
+        self.text_tower, self.tokenizer = text_tower, tokenizer
+        self._rows = {}
+
+    def lookup(self, prompts, device):
+        """[len(prompts), embed] fp32 on `device`"""
+        new = [p for p in dict.fromkeys(prompts) if p not in self._rows]
+        if new:
+            if not callable(self.tokenizer):                   # a directory: transformers is imported on first use only
+                from .text_encoders import load_tokenizer
+                self.tokenizer = load_tokenizer(self.tokenizer, self.text_tower.config.context)
+            feats = self.text_tower.encode_text(self.tokenizer(new)).detach().float()
+            if feats.dim() != 2 or feats.shape[0] != len(new):
+                raise ValueError(f"encode_text returned {tuple(feats.shape)} for {len(new)} prompts")
+            for p, row in zip(new, feats):
+                self._rows[p] = row.clone()
+        return torch.stack([self._rows[p] for p in prompts]).to(torch.device(device)).contiguous()
+
+
 class ClipReward:
     """`(images, prompts) -> list[float]`, the order reward_adapter.compute_reward uses.  Images are [3, H, W] device tensors as
-    AutoencoderKL.decode returns them (PIL images are converted on the host); `text_features` a TextFeatureCache."""
+    AutoencoderKL.decode returns them (PIL images are converted on the host); `text_features` a TextFeatureCache or a
+    TextTowerFeatures."""
 
     def __init__(self, tower, text_features, kind, mean=18.0, std=8.0):
         if kind not in KINDS:
@@ -129,7 +159,10 @@ class ClipReward:
 def builtin_rewards(args=None):
     """`--mgx_reward_plugin mixgrpo_amd.rewards:builtin_rewards`: reads the JSON file named by the environment variable
     MGX_REWARD_CONFIG, `{RewardClassName: {"tower_dir": ..., "text_features": ..., ["mean": 18.0, "std": 8.0, "device": "cuda"]}}`,
-    and returns `{RewardClassName: ClipReward}`.  Rewards that name the same tower directory share one tower."""
+    and returns `{RewardClassName: ClipReward}`.  Instead of `text_features` (a TextFeatureCache file) an entry may give
+    `"text_tower_dir"` (config.json + safetensors of the text tower; the image tower's directory if it holds a whole CLIPModel)
+    and optionally `"tokenizer_dir"` (default: the text tower's directory): prompts are then encoded as they come
+    (TextTowerFeatures).  Rewards that name the same directory share one tower."""
     from .clip_vision import ClipVisionTower
     path = os.environ.get(CONFIG_ENV)
     if not path:
@@ -142,13 +175,20 @@ def builtin_rewards(args=None):
     for name, c in cfg.items():
         if name not in KINDS:
             raise ValueError(f"{path}: {name!r} is not one of {KINDS}")
-        missing = [k for k in ("tower_dir", "text_features") if k not in c]
+        missing = [k for k in ("tower_dir", "text_features") if k not in c and not (k == "text_features" and "text_tower_dir" in c)]
         if missing:
             raise ValueError(f"{path}: {name} lacks {missing}")
         tkey = (c["tower_dir"], c.get("device", "cuda"))
         if tkey not in towers:
             towers[tkey] = ClipVisionTower.from_pretrained(*tkey)
-        if c["text_features"] not in caches:
-            caches[c["text_features"]] = TextFeatureCache(c["text_features"])
-        out[name] = ClipReward(towers[tkey], caches[c["text_features"]], name, c.get("mean", 18.0), c.get("std", 8.0))
+        if "text_features" in c:
+            ckey = c["text_features"]
+            if ckey not in caches:
+                caches[ckey] = TextFeatureCache(ckey)
+        else:
+            ckey = (c["text_tower_dir"], c.get("tokenizer_dir", c["text_tower_dir"]), tkey[1])
+            if ckey not in caches:
+                from .clip_text import ClipTextTower
+                caches[ckey] = TextTowerFeatures(ClipTextTower.from_pretrained(ckey[0], ckey[2]), ckey[1])
+        out[name] = ClipReward(towers[tkey], caches[ckey], name, c.get("mean", 18.0), c.get("std", 8.0))
     return out
