@@ -559,6 +559,32 @@ int mgx_gated_act_rows(const uint16_t* a, long lda, const uint16_t* b, long ldb,
 int mgx_token_embed(const int* ids, const uint16_t* table, const float* pos, uint16_t* x, long M, int S, int D, int V,
                     void* stream);
 
+/* ---- ImageReward scorer (csrc/blip.hip): the network behind the reference's ImageRewardModel
+ * (fastvideo/models/reward_model/image_reward.py:24-40; `self.model.inference_rank(text, [image])` :38): a BLIP ViT image
+ * encoder, a BERT text encoder whose layers cross-attend to the image tokens, an MLP head.  Inference only; the Linears are
+ * mgx_gemm_bf16 launches, LayerNorm, GELU and the embeddings the entry points above.
+ *
+ * Attention with separate operands and a key length per sample (image_reward.py:38: BertSelfAttention inside inference_rank,
+ * once over the padded prompt with its attention_mask, once over the image tokens as encoder_hidden_states).  Row b Sq + s of
+ * q [B Sq][ldq] holds head h in the columns h d, rows b Skv + t of k [B Skv][ldk] and v [B Skv][ldv] likewise;
+ * O[b Sq + s][h d ..] = bf16(softmax(scale q k^T over the keys t < kv_len[b]) v), ldo elements between rows.  kv_len: device
+ * int32 [B], or NULL: all Skv keys count.  mgx_vit_attn_fwd's arithmetic: bf16 MFMA, fp32 scores and sums, one rounding of O,
+ * no lse.  Excluded keys are excluded exactly (BERT's additive -10000 / finfo.min gives them a weight that underflows to 0):
+ * the k and v rows at or beyond kv_len[b] may hold anything, inf and NaN included -- they are not read, and key blocks wholly
+ * beyond kv_len[b] are neither loaded nor multiplied.  Contract: 1 <= kv_len[b] <= Skv (the Python wrapper checks it on the
+ * host before the copy); the kernel clamps into that range, so it never reads outside the rows [0, B Skv) and no query meets an
+ * empty key set.  d % 16 == 0, d <= 128; any Sq, Skv >= 1; every row stride a multiple of 8 elements, all four pointers 16-byte
+ * aligned; nothing outside the B Sq rows and the head columns of O is written.  q, k and v may point into one packed buffer.
+ * Returns 1 -- nothing launched -- for Sq > 4096 or Skv > 4096. */
+int mgx_xattn_fwd(const uint16_t* q, long ldq, const uint16_t* k, long ldk, const uint16_t* v, long ldv, uint16_t* O, long ldo,
+                  int B, int H, int Sq, int Skv, int d, float scale, const int* kv_len, void* stream);
+/* out[m][0..N) (fp32) = x[m][0..K) W[N][K]^T + bias, then, if affine != 0, (. - shift) / scale: the Linears of ImageReward's
+ * score head `self.mlp` and its `(rewards - self.mean) / self.std` (inside inference_rank, image_reward.py:38), applied layer by
+ * layer with fp32 intermediates.  x rows of bf16 or fp32 (`x_is_f32`), ldx elements apart (ldx % 4 == 0); W, bias (or NULL) and
+ * out fp32, out rows ldo apart.  fp32 products and sums.  Any M, N >= 1; K % 4 == 0. */
+int mgx_linear_rows_f32(const void* x, int x_is_f32, long ldx, const float* W, const float* bias, float* out, long ldo, int M,
+                        int N, int K, int affine, float shift, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,8 @@ SIGNATURES = {
     "mgx_rms_norm_affine": (_I, [_P, _L, _P, _P, _L, _L, _I, _F, _P]),
     "mgx_gated_act_rows": (_I, [_P, _L, _P, _L, _P, _L, _L, _I, _I, _P]),
     "mgx_token_embed": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    "mgx_xattn_fwd": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P, _P]),
+    "mgx_linear_rows_f32": (_I, [_P, _I, _L, _P, _P, _P, _L, _I, _I, _I, _I, _F, _F, _P]),
 }
 
 _lib = None

@@ -544,3 +544,49 @@ def token_embed(input_ids, table, pos, x):
         raise ValueError(f"{S} positions of width {D} need pos [>= {S}, {D}], not {tuple(pos.shape)}")
     ids = input_ids.to(device=table.device, dtype=torch.int32).contiguous()
     check(lib().mgx_token_embed(ptr(ids), ptr(table), ptr(pos), ptr(x), B * S, S, D, V, stream()))
+
+
+# ------------------------------------------------------------------------------------------------ ImageReward (csrc/blip.hip)
+def check_kv_len(kv_len, B, Skv):
+    """The contract of `mgx_xattn_fwd`'s key lengths, checked where the tensor is (normally the host): an integer tensor [B]
+    with every entry in [1, Skv]; anything else raises a ValueError that names it."""
+    if kv_len.dim() != 1 or kv_len.shape[0] != B or kv_len.dtype.is_floating_point or kv_len.dtype == torch.bool:
+        raise ValueError(f"kv_len must be an integer tensor [{B}], not {kv_len.dtype} {tuple(kv_len.shape)}")
+    bad = ((kv_len < 1) | (kv_len > Skv)).nonzero()
+    if bad.numel():
+        b = int(bad[0])
+        raise ValueError(f"key length {int(kv_len[b])} of sample {b} is outside [1, {Skv}]")
+
+
+def xattn_fwd(q, ldq, k, ldk, v, ldv, O, ldo, B, H, Sq, Skv, d, scale, kv_len=None, kv_len_checked=False):
+    """O[b Sq + s, h d:] = softmax(scale q k^T over the keys t < kv_len[b]) v with q, k, v in buffers of their own
+    (`mgx_xattn_fwd`); q, k, v, O: tensors whose data_ptr() is the first element, rows ldq / ldk / ldv / ldo elements apart.
+    `kv_len`: an integer tensor [B], normally on the host, or None (all Skv keys): the lengths are checked where they are
+    (`check_kv_len`), before the copy to the device -- nothing is launched on a bad one.  `kv_len_checked`: the caller has done
+    that already and passes the lengths on the device (a layer loop checks and copies once).  False -- nothing launched -- for
+    Sq > 4096 or Skv > 4096."""
+    lens = None
+    if kv_len is not None:
+        if not kv_len_checked:
+            check_kv_len(kv_len, B, Skv)
+        lens = kv_len.to(device=O.device, dtype=torch.int32).contiguous()
+    return _try(lib().mgx_xattn_fwd, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, O.data_ptr(), ldo, B, H, Sq, Skv, d,
+                float(scale), ptr(lens), stream())
+
+
+def linear_rows_f32(x, W, bias, out, shift=None, scale=None):
+    """out[M, N] (fp32) = x[M, K] @ W[N, K]^T + bias, then `(. - shift) / scale` when both are given (`mgx_linear_rows_f32`).
+    x bf16 or fp32 rows (stride(0) elements apart), W and bias (or None) fp32, out fp32 rows."""
+    if x.dtype not in (BF16, F32) or W.dtype != F32 or out.dtype != F32 or (bias is not None and bias.dtype != F32):
+        raise ValueError("linear_rows_f32 takes bf16 or fp32 rows and fp32 weights, bias and output")
+    if (shift is None) != (scale is None):
+        raise ValueError("give shift and scale, or neither")
+    M, K = x.shape
+    N = W.shape[0]
+    if W.shape[1] != K or tuple(out.shape) != (M, N) or (bias is not None and tuple(bias.shape) != (N,)):
+        raise ValueError(f"x {tuple(x.shape)} W {tuple(W.shape)} out {tuple(out.shape)} do not fit")
+    if x.stride(1) != 1 or out.stride(1) != 1:
+        raise ValueError("x and out must have unit column stride")
+    check(lib().mgx_linear_rows_f32(x.data_ptr(), int(x.dtype == F32), x.stride(0) if M > 1 else max(x.stride(0), K), ptr(W),
+                                    ptr(bias), out.data_ptr(), out.stride(0) if M > 1 else max(out.stride(0), N), M, N, K,
+                                    int(shift is not None), float(shift or 0.0), float(1.0 if scale is None else scale), stream()))

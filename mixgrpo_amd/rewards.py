@@ -15,6 +15,9 @@ same `lookup(prompts, device)`:
 Only the image tower runs on every step of the training loop: `decode -> ClipReward` stays on the device, with no PIL image and
 no host copy of one.
 
+The reference's fourth local reward, ImageRewardModel (image_reward.py:24-40), is not a CLIP: mixgrpo_amd/image_reward.py holds
+it, and `builtin_rewards` builds it from an entry of its own (IMAGE_REWARD).
+
 `builtin_rewards` is a factory for `--mgx_reward_plugin mixgrpo_amd.rewards:builtin_rewards`."""
 import json
 import os
@@ -24,6 +27,7 @@ import torch
 from . import ops
 
 KINDS = ("HPSClipRewardModel", "CLIPScoreRewardModel", "PickScoreRewardModel")
+IMAGE_REWARD = "ImageRewardModel"            # not one of KINDS: no ClipReward, an image_reward.ImageRewardModel
 CONFIG_ENV = "MGX_REWARD_CONFIG"
 
 
@@ -156,13 +160,29 @@ class ClipReward:
         return out.tolist()
 
 
+def _image_reward(path, c, args):
+    from . import image_reward
+    files = {"checkpoint": "image_reward_path", "med_config": "image_reward_med_config"}
+    given = {k: c.get(k) or getattr(args, a, None) for k, a in files.items()}
+    missing = [k for k, v in given.items() if not v]
+    if missing:
+        raise ValueError(f"{path}: {IMAGE_REWARD} lacks {missing}")
+    tok = c.get("tokenizer_dir", os.path.dirname(os.path.abspath(given["checkpoint"])))
+    return image_reward.ImageRewardModel.from_pretrained(given["checkpoint"], given["med_config"], tokenizer=tok,
+                                                         mean=c.get("mean", image_reward.MEAN), std=c.get("std", image_reward.STD),
+                                                         device=c.get("device", "cuda"))
+
+
 def builtin_rewards(args=None):
     """`--mgx_reward_plugin mixgrpo_amd.rewards:builtin_rewards`: reads the JSON file named by the environment variable
     MGX_REWARD_CONFIG, `{RewardClassName: {"tower_dir": ..., "text_features": ..., ["mean": 18.0, "std": 8.0, "device": "cuda"]}}`,
     and returns `{RewardClassName: ClipReward}`.  Instead of `text_features` (a TextFeatureCache file) an entry may give
     `"text_tower_dir"` (config.json + safetensors of the text tower; the image tower's directory if it holds a whole CLIPModel)
     and optionally `"tokenizer_dir"` (default: the text tower's directory): prompts are then encoded as they come
-    (TextTowerFeatures).  Rewards that name the same directory share one tower."""
+    (TextTowerFeatures).  Rewards that name the same directory share one tower.
+    An `"ImageRewardModel"` entry is `{"checkpoint": ..., "med_config": ..., ["tokenizer_dir", "mean", "std", "device"]}` and gives
+    an image_reward.ImageRewardModel; `checkpoint` and `med_config` default to `args.image_reward_path` and
+    `args.image_reward_med_config` when `args` carries them, `tokenizer_dir` to the checkpoint's directory."""
     from .clip_vision import ClipVisionTower
     path = os.environ.get(CONFIG_ENV)
     if not path:
@@ -173,8 +193,11 @@ def builtin_rewards(args=None):
         raise ValueError(f"{path}: expected a non-empty JSON object")
     towers, caches, out = {}, {}, {}
     for name, c in cfg.items():
+        if name == IMAGE_REWARD:
+            out[name] = _image_reward(path, c, args)
+            continue
         if name not in KINDS:
-            raise ValueError(f"{path}: {name!r} is not one of {KINDS}")
+            raise ValueError(f"{path}: {name!r} is not one of {KINDS + (IMAGE_REWARD,)}")
         missing = [k for k in ("tower_dir", "text_features") if k not in c and not (k == "text_features" and "text_tower_dir" in c)]
         if missing:
             raise ValueError(f"{path}: {name} lacks {missing}")
