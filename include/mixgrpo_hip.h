@@ -530,8 +530,9 @@ int mgx_cosine_score(const void* f, int f_is_f32, long ldf, const void* t, int t
  * encoders behind `pipe.encode_prompt` (fastvideo/data_preprocess/preprocess_flux_embedding.py:89).  Inference only; the Linears
  * are mgx_gemm_bf16 launches.
  *
- * mgx_vit_attn_fwd's contract and kernel body (packed q | k | v rows, bf16 MFMA, fp32 scores and sums, one rounding of O,
- * nothing read or written outside the rows and the head columns, d % 16 == 0, d <= 128, returns 1 for S > 4096), plus:
+ * mgx_vit_attn_fwd's contract and kernel (csrc/encoder_attn.hip: packed q | k | v rows, bf16 MFMA, fp32 scores and sums, one
+ * rounding of O, nothing read or written outside the rows and the head columns, d % 16 == 0, d <= 128, returns 1 for S > 4096),
+ * plus:
  *   causal != 0: key k contributes to query q only if k <= q (CLIPTextTransformer's causal mask / open_clip's attn_mask); key
  *                blocks wholly above a workgroup's last query are neither loaded nor multiplied;
  *   rel_bias (device fp32 [H][2 S - 1], or NULL): rel_bias[h][k - q + S - 1] is added to scale * q.k in fp32 before the maximum
@@ -568,8 +569,8 @@ int mgx_token_embed(const int* ids, const uint16_t* table, const float* pos, uin
  * once over the padded prompt with its attention_mask, once over the image tokens as encoder_hidden_states).  Row b Sq + s of
  * q [B Sq][ldq] holds head h in the columns h d, rows b Skv + t of k [B Skv][ldk] and v [B Skv][ldv] likewise;
  * O[b Sq + s][h d ..] = bf16(softmax(scale q k^T over the keys t < kv_len[b]) v), ldo elements between rows.  kv_len: device
- * int32 [B], or NULL: all Skv keys count.  mgx_vit_attn_fwd's arithmetic: bf16 MFMA, fp32 scores and sums, one rounding of O,
- * no lse.  Excluded keys are excluded exactly (BERT's additive -10000 / finfo.min gives them a weight that underflows to 0):
+ * int32 [B], or NULL: all Skv keys count.  mgx_vit_attn_fwd's kernel (csrc/encoder_attn.hip) and arithmetic: bf16 MFMA, fp32
+ * scores and sums, one rounding of O, no lse.  Excluded keys are excluded exactly (BERT's additive -10000 / finfo.min gives them a weight that underflows to 0):
  * the k and v rows at or beyond kv_len[b] may hold anything, inf and NaN included -- they are not read, and key blocks wholly
  * beyond kv_len[b] are neither loaded nor multiplied.  Contract: 1 <= kv_len[b] <= Skv (the Python wrapper checks it on the
  * host before the copy); the kernel clamps into that range, so it never reads outside the rows [0, B Skv) and no query meets an

@@ -7,22 +7,22 @@ and the CLIP-L text model whose `pooler_output` FLUX's `encode_prompt` takes
 
 Layout, as clip_vision.py: all prompts of a call are one batch of M = B S token rows, bf16; every Linear is a launch of the
 persistent GEMM (`ops.gemm(..., stream_k=False)`, so that a prompt's rows do not depend on how many prompts share the call),
-residual sums ride the GEMM epilogue with a ones gate; csrc/text.hip holds the token + position embedding and the causal
-attention that reads the packed q | k | v projection, csrc/clip.hip LayerNorm and the exact / quick GELU.  EOS pooling needs
+residual sums ride the GEMM epilogue with a ones gate (encoder_host.py: the host scaffold shared with the other encoders);
+csrc/text.hip holds the token + position embedding, csrc/encoder_attn.hip the causal attention that reads the packed q | k | v
+projection, csrc/clip.hip LayerNorm and the exact / quick GELU.  EOS pooling needs
 no kernel: the positions are known on the host, the final LayerNorm runs on all rows and `index_select` picks the pooled ones.
 
 Weights: HF `CLIPModel` / `CLIPTextModelWithProjection` / `CLIPTextModel` key names (pinned against transformers by
 tests/test_text_refs.py) or open_clip's names (recollected: the library is absent offline, PARITY UNPINNED), both converted to
 one internal layout with the fused q | k | v weight [3 width, width] (`convert_state_dict`).  The tokenizer is not part of this
 module: every entry point takes token ids (text_encoders.load_tokenizer delegates tokenising to transformers)."""
-import json
-import os
 from dataclasses import dataclass, replace
 
 import torch
 
 from . import ops
-from .ops import BF16, F32, Rows, EPI_BIAS_GATE_RES
+from .encoder_host import EncoderHost, convert_names, draw_state_dict, layer_norm_net_std, read_checkpoint_dir
+from .ops import F32
 
 ACTS = {"gelu": ops.ACT_GELU, "quick_gelu": ops.ACT_QUICK_GELU}
 
@@ -119,29 +119,11 @@ def convert_state_dict(sd, config):
     fused, open_clip's `text_projection` is transposed to [embed, width].  Tensors of the text tower that are missing, of the
     wrong shape, or text-tower tensors the layout does not know raise a ValueError that names them; image-tower tensors are
     ignored.  `text_projection` alone may be absent (a bare CLIPTextModel): `encode_text` then raises, `pooled_output` works."""
-    hf = any(k.startswith("text_model.") for k in sd)
-    names = _hf_names(config) if hf else _open_clip_names(config)
-    prefix = ("text_model.", "text_projection.") if hf else _OPEN_CLIP_OWN
-    out, missing, used = {}, [], set()
-    for name, src in names.items():
-        parts = src if isinstance(src, tuple) else (src,)
-        miss = [p for p in parts if p not in sd]
-        if miss:
-            if name not in OPTIONAL:
-                missing += miss
-            continue
-        used.update(parts)
-        t = torch.cat([sd[p] for p in parts], 0) if len(parts) > 1 else sd[parts[0]]
-        if name == "proj.weight" and not hf:
-            t = t.t()
-        out[name] = t
-    unknown = sorted(k for k in sd if k.startswith(prefix) and k not in used and not k.endswith("position_ids"))
-    if missing or unknown:
-        raise ValueError(f"CLIP text state dict: missing {sorted(missing)[:8]} ({len(missing)}), unknown {unknown[:8]} ({len(unknown)})")
-    bad = [f"{k} {tuple(out[k].shape)} != {shp}" for k, shp in param_shapes(config).items()
-           if k in out and tuple(out[k].shape) != tuple(shp)]
-    if bad:
-        raise ValueError(f"CLIP text state dict: wrong shapes: {bad[:8]}")
+    if any(k.startswith("text_model.") for k in sd):
+        names, own, fixups = _hf_names(config), ("text_model.", "text_projection."), None
+    else:
+        names, own, fixups = _open_clip_names(config), _OPEN_CLIP_OWN, {"proj.weight": lambda t: t.t()}
+    out = convert_names(sd, names, param_shapes(config), own, "CLIP text", OPTIONAL, fixups)
     ls = sd.get("logit_scale")
     return out, (None if ls is None else float(ls))
 
@@ -168,69 +150,30 @@ def pooled_positions(input_ids, eos_token_id):
     return (ids == eos_token_id).int().argmax(dim=-1)
 
 
-def _read_dir(path):
-    from safetensors.torch import load_file
-    with open(os.path.join(path, "config.json")) as f:
-        raw = json.load(f)
-    files = sorted(f for f in os.listdir(path) if f.endswith(".safetensors"))
-    if not files:
-        raise FileNotFoundError(f"no *.safetensors file in {path}")
-    sd = {}
-    for f in files:
-        sd.update(load_file(os.path.join(path, f)))
-    return raw, sd
-
-
-class ClipTextTower:
+class ClipTextTower(EncoderHost):
     def __init__(self, config: ClipTextConfig = None, device="cuda"):
         self.config = (config or CLIP_L_TEXT).check()
-        self.device = torch.device(device)
-        self.P = None
+        super().__init__(device, self.config.width)
         self.logit_scale = None
-        self._buf = {}
-        self._ones = torch.ones(max(self.config.width, 512), dtype=BF16, device=self.device)
 
     # ---------------------------------------------------------------------------------------------- weights
     @classmethod
     def from_pretrained(cls, path, device="cuda"):
         """A directory with `config.json` (see `config_from_json`) and one or more `*.safetensors` files in HF or open_clip key
         names; a whole CLIPModel checkpoint loads here and into ClipVisionTower alike."""
-        raw, sd = _read_dir(path)
+        raw, sd = read_checkpoint_dir(path)
         return cls(config_from_json(raw), device=device).load_state_dict(sd)
-
-    def to(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag=False):
-        return self
 
     def load_state_dict(self, sd):
         """HF or open_clip names (`convert_state_dict`).  Matrices, biases and the token table go to bf16 (the GEMM's operands,
         the gather's rows), LayerNorm parameters and position embeddings stay fp32."""
-        dev = self.device
         t, self.logit_scale = convert_state_dict(sd, self.config)
-        P = {}
-        for k, v in t.items():
-            v = v.to(dev)
-            fp32 = k == "pos" or ".ln_" in k or k.startswith("ln_")
-            P[k] = v.to(F32 if fp32 else BF16).contiguous()
-        self.P = P
+        self.P = self._place(t)
         return self
 
     def init_synthetic(self, seed=0):
         """Random weights of the configured architecture drawn on the tower's device, every value a bf16 number, HF key names."""
         return self.load_state_dict(synthetic_state_dict(self.config, seed, self.device))
-
-    # ---------------------------------------------------------------------------------------------- buffers
-    def _plain(self, tag, M, C, dtype=BF16):
-        key = (tag, M, C, dtype)
-        t = self._buf.get(key)
-        if t is None:
-            t = self._buf[key] = torch.empty(M, C, dtype=dtype, device=self.device)
-        return t
 
     # ---------------------------------------------------------------------------------------------- forward
     def _hidden(self, input_ids):
@@ -243,22 +186,24 @@ class ClipTextTower:
         B, S = input_ids.shape
         w, H, d, mlp, eps = c.width, c.heads, c.head_dim, c.mlp_width, c.layer_norm_eps
         M = B * S
-        gemm = lambda a, W, b, out, N, K, **kw: ops.gemm(Rows.of(a), W, b, Rows.of(out), N, K, stream_k=False, **kw)
         x = self._plain("x", M, w)
         ops.token_embed(input_ids, P["tok"], P["pos"], x)       # checks the ids on the host first: nothing launched on a bad one
         n, qkv, o, h = self._plain("n", M, w), self._plain("qkv", M, 3 * w), self._plain("o", M, w), self._plain("h", M, mlp)
-        for i in range(c.layers):
-            L = f"layers.{i}."
-            ops.layer_norm_affine(x, w, P[L + "ln_1.weight"], P[L + "ln_1.bias"], n, w, M, w, eps)
-            gemm(n, P[L + "qkv.weight"], P[L + "qkv.bias"], qkv, 3 * w, w)
+
+        def norm(src, name, dst):
+            self._layer_norm(src, name, dst, M, w, eps)
+
+        def attend(qkv, o):
             if not ops.text_attn_fwd(qkv, 3 * w, o, w, B, H, S, d, d ** -0.5, causal=True):
                 raise RuntimeError(f"mgx_text_attn_fwd refused {S} tokens")
-            gemm(o, P[L + "out.weight"], P[L + "out.bias"], x, w, w, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
-            ops.layer_norm_affine(x, w, P[L + "ln_2.weight"], P[L + "ln_2.bias"], n, w, M, w, eps)
-            gemm(n, P[L + "fc1.weight"], P[L + "fc1.bias"], h, mlp, w)
+
+        def activate(h):
             ops.act_rows(h, mlp, h, mlp, M, mlp, ACTS[c.act])
-            gemm(h, P[L + "fc2.weight"], P[L + "fc2.bias"], x, w, mlp, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
-        ops.layer_norm_affine(x, w, P["ln_final.weight"], P["ln_final.bias"], n, w, M, w, eps)
+            return h
+
+        for i in range(c.layers):
+            self._prenorm_layer(f"layers.{i}.", x, n, qkv, o, h, norm, attend, activate)
+        norm(x, "ln_final", n)
         return n
 
     @torch.no_grad()
@@ -289,21 +234,6 @@ class ClipTextTower:
 
 def synthetic_state_dict(config, seed=0, device="cpu"):
     """A random HF-named state dict of `config`, drawn on `device`, every value a bf16 number held in fp32; logit_scale = ln 100."""
-    g = torch.Generator(device=device).manual_seed(seed)
-    r = lambda shp, std: (std * torch.randn(shp, generator=g, device=device)).to(BF16).float()
-    sd = {}
-    shapes = param_shapes(config)
-    for name, src in _hf_names(config).items():
-        shp = shapes[name]
-        for key in (src if isinstance(src, tuple) else (src,)):
-            s = (shp[0] // 3,) + tuple(shp[1:]) if isinstance(src, tuple) else shp
-            if name in ("tok", "pos"):
-                sd[key] = r(s, 0.5)
-            elif name.endswith("weight") and len(shp) == 1:
-                sd[key] = (1.0 + 0.1 * torch.randn(s, generator=g, device=device)).to(BF16).float()
-            elif name.endswith("bias"):
-                sd[key] = r(s, 0.05)
-            else:
-                sd[key] = r(s, s[1] ** -0.5)
+    sd = draw_state_dict(_hf_names(config), param_shapes(config), layer_norm_net_std, seed, device)
     sd["logit_scale"] = torch.tensor(4.605170185988092)
     return sd

@@ -7,8 +7,10 @@ Only the image tower runs in the training loop; the text feature of a prompt is 
 Layout: all images of a call are one batch of M = B S token rows, bf16; every Linear is a launch of the persistent GEMM
 (`ops.gemm`, without its stream-K workspace, so that an image's rows do not depend on how many images share the call), residual
 sums ride the GEMM epilogue with a ones gate, as vae._attention does; csrc/clip.hip holds the rest: the preprocessing (PIL's
-antialiased bicubic resize, crop, normalise, patch rows), the embedding, LayerNorm, the attention that reads the packed q | k | v
-projection, the exact / quick GELU and the scores' tail.
+antialiased bicubic resize, crop, normalise, patch rows), the embedding, LayerNorm, the exact / quick GELU and the scores' tail;
+csrc/encoder_attn.hip the attention that reads the packed q | k | v projection.  The host scaffold (checkpoint reader, key
+conversion, synthetic weights, buffers, the Linear launch, the pre-norm layer) is encoder_host.py's, shared with the other
+encoders; `VitTrunk` here is the ViT up to its last layer, which image_reward.BlipVisionEncoder runs as well.
 
 Weights: HF `CLIPModel` / `CLIPVisionModelWithProjection` key names (pinned against transformers by tests/test_clip_refs.py) or
 open_clip's `visual.*` names (recollected: the library is absent offline, PARITY UNPINNED), both converted to one internal
@@ -21,7 +23,8 @@ from typing import Tuple
 import torch
 
 from . import ops
-from .ops import BF16, F32, Rows, EPI_BIAS_GATE_RES
+from .encoder_host import EncoderHost, convert_names, draw_state_dict, layer_norm_net_std, read_checkpoint_dir
+from .ops import BF16, F32
 
 OPENAI_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -126,27 +129,11 @@ def convert_state_dict(sd, config):
     """A state dict in HF or open_clip names -> (internal dict, logit_scale or None).  Tensors keep their dtype; q | k | v are
     fused, open_clip's `visual.proj` is transposed to [embed, width].  Tensors of the tower that are missing, of the wrong shape,
     or vision-tower tensors the layout does not know raise a ValueError that names them; text-tower tensors are ignored."""
-    hf = any(k.startswith("vision_model.") for k in sd)
-    names = _hf_names(config) if hf else _open_clip_names(config)
-    prefix = ("vision_model.", "visual_projection.") if hf else ("visual.",)
-    out, missing, used = {}, [], set()
-    for name, src in names.items():
-        parts = src if isinstance(src, tuple) else (src,)
-        miss = [p for p in parts if p not in sd]
-        if miss:
-            missing += miss
-            continue
-        used.update(parts)
-        t = torch.cat([sd[p] for p in parts], 0) if len(parts) > 1 else sd[parts[0]]
-        if name == "proj.weight" and not hf:
-            t = t.t()
-        out[name] = t
-    unknown = sorted(k for k in sd if k.startswith(prefix) and k not in used and not k.endswith("position_ids"))
-    if missing or unknown:
-        raise ValueError(f"CLIP vision state dict: missing {sorted(missing)[:8]} ({len(missing)}), unknown {unknown[:8]} ({len(unknown)})")
-    bad = [f"{k} {tuple(out[k].shape)} != {shp}" for k, shp in param_shapes(config).items() if tuple(out[k].shape) != tuple(shp)]
-    if bad:
-        raise ValueError(f"CLIP vision state dict: wrong shapes: {bad[:8]}")
+    if any(k.startswith("vision_model.") for k in sd):
+        names, own, fixups = _hf_names(config), ("vision_model.", "visual_projection."), None
+    else:
+        names, own, fixups = _open_clip_names(config), ("visual.",), {"proj.weight": lambda t: t.t()}
+    out = convert_names(sd, names, param_shapes(config), own, "CLIP vision", fixups=fixups)
     ls = sd.get("logit_scale")
     return out, (None if ls is None else float(ls))
 
@@ -179,81 +166,27 @@ def pil_pixel_values(image, config):
     return (a / 255.0 - mean) / std
 
 
-class ClipVisionTower:
-    def __init__(self, config: ClipVisionConfig = None, device="cuda"):
-        self.config = (config or VIT_H_14).check()
-        self.device = torch.device(device)
-        self.P = None
-        self.logit_scale = None
-        self._buf = {}
-        self._ones = torch.ones(max(self.config.width, 512), dtype=BF16, device=self.device)
+class VitTrunk(EncoderHost):
+    """The ViT both image encoders run (ClipVisionTower here, image_reward.BlipVisionEncoder): preprocessing, the padded patch
+    weight, and patch GEMM (bias optional) -> `vit_embed` -> `ln_pre` if the network has one -> the pre-norm layers.  `P` is
+    the internal layout of `param_shapes`; what follows the last layer is the subclass's."""
+    label = "CLIP vision"
 
-    # ---------------------------------------------------------------------------------------------- weights
-    @classmethod
-    def from_pretrained(cls, path, device="cuda"):
-        """A directory with `config.json` (see `config_from_json`), optionally `preprocessor_config.json` (image_mean / image_std)
-        and one or more `*.safetensors` files in HF or open_clip key names."""
-        from safetensors.torch import load_file
-        with open(os.path.join(path, "config.json")) as f:
-            cfg = config_from_json(json.load(f))
-        pp = os.path.join(path, "preprocessor_config.json")
-        if os.path.exists(pp):
-            with open(pp) as f:
-                raw = json.load(f)
-            if "image_mean" in raw and "image_std" in raw:
-                cfg = replace(cfg, image_mean=tuple(raw["image_mean"]), image_std=tuple(raw["image_std"]))
-        files = sorted(f for f in os.listdir(path) if f.endswith(".safetensors"))
-        if not files:
-            raise FileNotFoundError(f"no *.safetensors file in {path}")
-        sd = {}
-        for f in files:
-            sd.update(load_file(os.path.join(path, f)))
-        return cls(cfg, device=device).load_state_dict(sd)
+    def __init__(self, config, device="cuda"):
+        self.config = config.check()
+        super().__init__(device, self.config.width)
 
-    def to(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag=False):
-        return self
-
-    def load_state_dict(self, sd):
-        """HF or open_clip names (`convert_state_dict`).  Matrices and biases go to bf16 (the GEMM's operands), LayerNorm
-        parameters, class token and position embeddings stay fp32; the patch weight is flattened to [width, 3 p p] and
-        zero-padded to the GEMM's K % 64 == 0."""
-        c, dev = self.config, self.device
-        t, self.logit_scale = convert_state_dict(sd, c)
-        P = {}
-        Kp = ops.clip_patch_cols(c.patch_size)
-        for k, v in t.items():
-            v = v.to(dev)
-            if k == "patch.weight":
-                w = torch.zeros(c.width, Kp, dtype=BF16, device=dev)
-                w[:, :3 * c.patch_size ** 2] = v.reshape(c.width, -1).to(BF16)
-                P[k] = w
-            elif k in ("cls", "pos") or ".ln_" in k or k.startswith("ln_"):
-                P[k] = v.to(F32).contiguous()
-            else:
-                P[k] = v.to(BF16).contiguous()
+    def _load(self, t):
+        """A converted dict onto the device (`_place`); the patch weight is flattened to [width, 3 p p] and zero-padded to the
+        GEMM's K % 64 == 0."""
+        c = self.config
+        P = self._place({k: v for k, v in t.items() if k != "patch.weight"})
+        w = torch.zeros(c.width, ops.clip_patch_cols(c.patch_size), dtype=BF16, device=self.device)
+        w[:, :3 * c.patch_size ** 2] = t["patch.weight"].to(self.device).reshape(c.width, -1).to(BF16)
+        P["patch.weight"] = w
         self.P = P
         return self
 
-    def init_synthetic(self, seed=0):
-        """Random weights of the configured architecture drawn on the tower's device, every value a bf16 number (no checkpoint
-        offline), HF key names."""
-        return self.load_state_dict(synthetic_state_dict(self.config, seed, self.device))
-
-    # ---------------------------------------------------------------------------------------------- buffers
-    def _plain(self, tag, M, C, dtype=BF16):
-        key = (tag, M, C, dtype)
-        t = self._buf.get(key)
-        if t is None:
-            t = self._buf[key] = torch.empty(M, C, dtype=dtype, device=self.device)
-        return t
-
-    # ---------------------------------------------------------------------------------------------- forward
     def preprocess(self, images):
         """Decoded images ([3, H, W] device tensors in about [-1, 1], a list or a [B, 3, H, W] tensor; sizes may differ) -> patch
         rows [B (R / p)^2, Kp] bf16, a shared buffer.  PIL images are resized by PIL on the host, as the reference does."""
@@ -282,12 +215,11 @@ class ClipVisionTower:
         out[:, :3 * p * p] = rows
         return out
 
-    @torch.no_grad()
-    def encode_image(self, images=None, pixel_values=None, normalize=True):
-        """-> [B, embed_dim] fp32: the projected class token (bf16 values), L2-normalised if `normalize`.  Give decoded `images`
-        (see `preprocess`) or `pixel_values` [B, 3, R, R] already resized and normalised."""
+    def _trunk(self, images, pixel_values, act):
+        """Decoded `images` (see `preprocess`) or `pixel_values` [B, 3, R, R] already resized and normalised -> (the residual
+        stream after the last layer [B tokens, width] bf16, a shared buffer; B).  `act`: the MLP's activation (ops.ACT_*)."""
         if self.P is None:
-            raise RuntimeError("CLIP vision weights not loaded")
+            raise RuntimeError(f"{self.label} weights not loaded")
         if (images is None) == (pixel_values is None):
             raise ValueError("give images or pixel_values")
         c, P = self.config, self.P
@@ -295,28 +227,73 @@ class ClipVisionTower:
         w, S, H, d, mlp, eps = c.width, c.tokens, c.heads, c.head_dim, c.mlp_width, c.layer_norm_eps
         B = patches.shape[0] // (S - 1)
         M = B * S
-        gemm = lambda a, W, b, out, N, K, **kw: ops.gemm(Rows.of(a), W, b, Rows.of(out), N, K, stream_k=False, **kw)
         pe = self._plain("patch_out", B * (S - 1), w)
-        gemm(patches, P["patch.weight"], None, pe, w, patches.shape[1])
+        self._linear(patches, "patch", pe)
         x = self._plain("x", M, w)
         ops.vit_embed(pe, P["cls"], P["pos"], x, B, S, w)
-        ops.layer_norm_affine(x, w, P["ln_pre.weight"], P["ln_pre.bias"], x, w, M, w, eps)
+        if "ln_pre.weight" in P:
+            self._layer_norm(x, "ln_pre", x, M, w, eps)
         n, qkv, o, h = self._plain("n", M, w), self._plain("qkv", M, 3 * w), self._plain("o", M, w), self._plain("h", M, mlp)
-        for i in range(c.layers):
-            L = f"layers.{i}."
-            ops.layer_norm_affine(x, w, P[L + "ln_1.weight"], P[L + "ln_1.bias"], n, w, M, w, eps)
-            gemm(n, P[L + "qkv.weight"], P[L + "qkv.bias"], qkv, 3 * w, w)
+
+        def norm(src, name, dst):
+            self._layer_norm(src, name, dst, M, w, eps)
+
+        def attend(qkv, o):
             if not ops.vit_attn_fwd(qkv, 3 * w, o, w, B, H, S, d, d ** -0.5):
                 raise RuntimeError(f"mgx_vit_attn_fwd refused {S} tokens")
-            gemm(o, P[L + "out.weight"], P[L + "out.bias"], x, w, w, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
-            ops.layer_norm_affine(x, w, P[L + "ln_2.weight"], P[L + "ln_2.bias"], n, w, M, w, eps)
-            gemm(n, P[L + "fc1.weight"], P[L + "fc1.bias"], h, mlp, w)
-            ops.act_rows(h, mlp, h, mlp, M, mlp, ACTS[c.act])
-            gemm(h, P[L + "fc2.weight"], P[L + "fc2.bias"], x, w, mlp, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
+
+        def activate(h):
+            ops.act_rows(h, mlp, h, mlp, M, mlp, act)
+            return h
+
+        for i in range(c.layers):
+            self._prenorm_layer(f"layers.{i}.", x, n, qkv, o, h, norm, attend, activate)
+        return x, B
+
+
+class ClipVisionTower(VitTrunk):
+    def __init__(self, config: ClipVisionConfig = None, device="cuda"):
+        super().__init__(config or VIT_H_14, device)
+        self.logit_scale = None
+
+    # ---------------------------------------------------------------------------------------------- weights
+    @classmethod
+    def from_pretrained(cls, path, device="cuda"):
+        """A directory with `config.json` (see `config_from_json`), optionally `preprocessor_config.json` (image_mean / image_std)
+        and one or more `*.safetensors` files in HF or open_clip key names."""
+        raw, sd = read_checkpoint_dir(path)
+        cfg = config_from_json(raw)
+        pp = os.path.join(path, "preprocessor_config.json")
+        if os.path.exists(pp):
+            with open(pp) as f:
+                raw = json.load(f)
+            if "image_mean" in raw and "image_std" in raw:
+                cfg = replace(cfg, image_mean=tuple(raw["image_mean"]), image_std=tuple(raw["image_std"]))
+        return cls(cfg, device=device).load_state_dict(sd)
+
+    def load_state_dict(self, sd):
+        """HF or open_clip names (`convert_state_dict`).  Matrices and biases go to bf16 (the GEMM's operands), LayerNorm
+        parameters, class token and position embeddings stay fp32; the patch weight is flattened and padded (`_load`)."""
+        t, self.logit_scale = convert_state_dict(sd, self.config)
+        return self._load(t)
+
+    def init_synthetic(self, seed=0):
+        """Random weights of the configured architecture drawn on the tower's device, every value a bf16 number (no checkpoint
+        offline), HF key names."""
+        return self.load_state_dict(synthetic_state_dict(self.config, seed, self.device))
+
+    # ---------------------------------------------------------------------------------------------- forward
+    @torch.no_grad()
+    def encode_image(self, images=None, pixel_values=None, normalize=True):
+        """-> [B, embed_dim] fp32: the projected class token (bf16 values), L2-normalised if `normalize`.  Give decoded `images`
+        (see `preprocess`) or `pixel_values` [B, 3, R, R] already resized and normalised."""
+        c = self.config
+        x, B = self._trunk(images, pixel_values, ACTS[c.act])
+        w = c.width
         pooled = self._plain("pooled", B, w)
-        ops.layer_norm_affine(x, S * w, P["ln_post.weight"], P["ln_post.bias"], pooled, w, B, w, eps)    # the class rows
+        self._layer_norm(x, "ln_post", pooled, B, w, c.layer_norm_eps, ldx=c.tokens * w)                  # the class rows
         feat = self._plain("feat", B, c.embed_dim)
-        ops.skinny_linear(pooled, P["proj.weight"], None, feat, c.embed_dim, w)
+        ops.skinny_linear(pooled, self.P["proj.weight"], None, feat, c.embed_dim, w)
         if not normalize:
             return feat.float()
         out = torch.empty(B, c.embed_dim, dtype=F32, device=self.device)
@@ -326,23 +303,6 @@ class ClipVisionTower:
 
 def synthetic_state_dict(config, seed=0, device="cpu"):
     """A random HF-named state dict of `config`, drawn on `device`, every value a bf16 number held in fp32; logit_scale = ln 100."""
-    g = torch.Generator(device=device).manual_seed(seed)
-    r = lambda shp, std: (std * torch.randn(shp, generator=g, device=device)).to(BF16).float()
-    sd = {}
-    for name, src in _hf_names(config).items():
-        shp = param_shapes(config)[name]
-        for j, key in enumerate(src if isinstance(src, tuple) else (src,)):
-            s = (shp[0] // 3,) + tuple(shp[1:]) if isinstance(src, tuple) else shp
-            if name in ("cls", "pos"):
-                sd[key] = r(s, 0.5)
-            elif name.endswith("weight") and len(shp) == 1:
-                sd[key] = (1.0 + 0.1 * torch.randn(s, generator=g, device=device)).to(BF16).float()
-            elif name.endswith("bias"):
-                sd[key] = r(s, 0.05)
-            else:
-                fan_in = 1
-                for v in s[1:]:
-                    fan_in *= v
-                sd[key] = r(s, fan_in ** -0.5)
+    sd = draw_state_dict(_hf_names(config), param_shapes(config), layer_norm_net_std, seed, device)
     sd["logit_scale"] = torch.tensor(4.605170185988092)
     return sd

@@ -1,20 +1,15 @@
 // CLIP ViT image tower (the reward networks of fastvideo/models/reward_model/{hps_score,pick_score,clip_score}.py): what sits
-// around the tower's Linears, which all run on the GEMM kernels (gemm.hip).  The tower is inference only.
+// around the tower's Linears, which all run on the GEMM kernels (gemm.hip), and its attention (mgx_vit_attn_fwd,
+// encoder_attn.hip).  The tower is inference only.
 //   mgx_clip_preprocess    decoded image -> normalised patch rows (the PIL resize + crop + normalise of the reference's processors)
 //   mgx_vit_embed          class token + patch embeddings + position embeddings
 //   mgx_layer_norm_affine  nn.LayerNorm with weight and bias
-//   mgx_vit_attn_fwd       non-causal multi-head attention straight from the packed q | k | v projection
 //   mgx_act_rows           exact GELU / QuickGELU
 //   mgx_l2_normalize_rows, mgx_cosine_score   the scores' tail
 #include "../../include/mixgrpo_hip.h"
 #include "common.h"
-#include "vit_attn.h"
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------------------- attention
-// vit_attn_kernel (vit_attn.h) is shared with the text towers' attention (text.hip); the image tower launches its instance
-// without mask and bias.
 
 // ------------------------------------------------------------------------------------------------------------- LayerNorm
 // one wave per row, element lane + 64 i on lane: fp32 mean, then the centred sum of squares (two passes over registers)
@@ -233,24 +228,6 @@ inline void resized_hw(int H, int W, int R, int* oh, int* ow) {
 }
 
 }  // namespace
-
-extern "C" int mgx_vit_attn_fwd(const uint16_t* qkv, long ld_qkv, uint16_t* O, long ldo, int B, int H, int S, int d, float scale,
-                                void* stream) {
-  const int rc = vit_attn_check(qkv, ld_qkv, O, ldo, B, H, S, d);
-  if (rc != MGX_OK) return rc;                                   // 1: S > 4096, refused, nothing launched
-  const int width = H * d;
-  const int nqb = (S + 63) / 64;
-  const int grid = B * H * nqb;
-  const float sl2 = scale * 1.4426950408889634f;
-  hipStream_t st = (hipStream_t)stream;
-  const int dp = (d + 31) / 32 * 32;
-  if (dp == 32) vit_attn_kernel<32, false, false><<<grid, 256, 0, st>>>(qkv, ld_qkv, O, ldo, H, S, d, width, sl2);
-  else if (dp == 64) vit_attn_kernel<64, false, false><<<grid, 256, 0, st>>>(qkv, ld_qkv, O, ldo, H, S, d, width, sl2);
-  else if (dp == 96) vit_attn_kernel<96, false, false><<<grid, 256, 0, st>>>(qkv, ld_qkv, O, ldo, H, S, d, width, sl2);
-  else vit_attn_kernel<128, false, false><<<grid, 256, 0, st>>>(qkv, ld_qkv, O, ldo, H, S, d, width, sl2);
-  MGX_CHECK_LAUNCH();
-  return MGX_OK;
-}
 
 extern "C" int mgx_layer_norm_affine(const uint16_t* x, long ldx, const float* gamma, const float* beta, uint16_t* y, long ldy,
                                      long M, int D, float eps, void* stream) {

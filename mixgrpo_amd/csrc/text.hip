@@ -1,32 +1,13 @@
 // Text encoders (the CLIP text tower of the reward networks, fastvideo/models/reward_model/{hps_score,pick_score,clip_score}.py,
 // and the T5 + CLIP-L prompt encoders of fastvideo/data_preprocess/preprocess_flux_embedding.py): what sits around their
-// Linears, which all run on the GEMM kernels (gemm.hip).  Inference only.
-//   mgx_text_attn_fwd     mgx_vit_attn_fwd's body (vit_attn.h) with a causal mask (CLIP text) or a relative-position bias (T5)
+// Linears, which all run on the GEMM kernels (gemm.hip), and their attention (mgx_text_attn_fwd, encoder_attn.hip).  Inference only.
 //   mgx_rms_norm_affine   T5LayerNorm
 //   mgx_gated_act_rows    act(a) * b: T5 v1.1's gated GELU
 //   mgx_token_embed       token-embedding gather + position embeddings
 #include "../../include/mixgrpo_hip.h"
 #include "common.h"
-#include "vit_attn.h"
 
 namespace {
-
-// the BIAS instances take the table as their last argument, the others have the image tower's argument list
-template <int DP, bool CAUSAL>
-void launch_text_attn(int grid, hipStream_t st, const bf16_raw* qkv, long ld, bf16_raw* O, long ldo, int H, int S, int d, int width,
-                      float sl2, const float* rel_bias) {
-  if (rel_bias) vit_attn_kernel<DP, CAUSAL, true><<<grid, 256, 0, st>>>(qkv, ld, O, ldo, H, S, d, width, sl2, rel_bias);
-  else vit_attn_kernel<DP, CAUSAL, false><<<grid, 256, 0, st>>>(qkv, ld, O, ldo, H, S, d, width, sl2);
-}
-
-template <bool CAUSAL>
-void launch_text_attn(int dp, int grid, hipStream_t st, const bf16_raw* qkv, long ld, bf16_raw* O, long ldo, int H, int S, int d,
-                      int width, float sl2, const float* rel_bias) {
-  if (dp == 32) launch_text_attn<32, CAUSAL>(grid, st, qkv, ld, O, ldo, H, S, d, width, sl2, rel_bias);
-  else if (dp == 64) launch_text_attn<64, CAUSAL>(grid, st, qkv, ld, O, ldo, H, S, d, width, sl2, rel_bias);
-  else if (dp == 96) launch_text_attn<96, CAUSAL>(grid, st, qkv, ld, O, ldo, H, S, d, width, sl2, rel_bias);
-  else launch_text_attn<128, CAUSAL>(grid, st, qkv, ld, O, ldo, H, S, d, width, sl2, rel_bias);
-}
 
 // ---------------------------------------------------------------------------------------------------------------- RMS norm
 // one wave per row, element lane + 64 i on lane (up to 64 per lane: D <= 4096): fp32 sum of squares, one rounding
@@ -98,22 +79,6 @@ __global__ void __launch_bounds__(256) token_embed_kernel(const int* __restrict_
 inline int ew_grid(long total) { return (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096); }
 
 }  // namespace
-
-extern "C" int mgx_text_attn_fwd(const uint16_t* qkv, long ld_qkv, uint16_t* O, long ldo, int B, int H, int S, int d, float scale,
-                                 int causal, const float* rel_bias, void* stream) {
-  if (!causal && !rel_bias) return mgx_vit_attn_fwd(qkv, ld_qkv, O, ldo, B, H, S, d, scale, stream);   // the image tower's kernel itself
-  const int rc = vit_attn_check(qkv, ld_qkv, O, ldo, B, H, S, d);
-  if (rc != MGX_OK) return rc;                                   // 1: S > 4096, refused, nothing launched
-  const int width = H * d;
-  const int grid = B * H * ((S + 63) / 64);
-  const float sl2 = scale * 1.4426950408889634f;
-  hipStream_t st = (hipStream_t)stream;
-  const int dp = (d + 31) / 32 * 32;
-  if (causal) launch_text_attn<true>(dp, grid, st, qkv, ld_qkv, O, ldo, H, S, d, width, sl2, rel_bias);
-  else launch_text_attn<false>(dp, grid, st, qkv, ld_qkv, O, ldo, H, S, d, width, sl2, rel_bias);
-  MGX_CHECK_LAUNCH();
-  return MGX_OK;
-}
 
 extern "C" int mgx_rms_norm_affine(const uint16_t* x, long ldx, const float* gamma, uint16_t* y, long ldy, long M, int D, float eps,
                                    void* stream) {

@@ -10,11 +10,12 @@ Inference only.
 
 Layout, as clip_vision.py and clip_text.py: all pairs of a call are one batch of token rows, bf16; every Linear of the two
 encoders is a launch of the persistent GEMM without its stream-K workspace (a pair's rows do not depend on what shares the
-call), residual sums ride the GEMM epilogue with a ones gate.  The image tokens are the same for every text layer, so the
-cross-attention keys and values of ALL layers come from ONE GEMM, weight [layers x 2 x width, encoder_width]; layer i reads its
-K and V out of that buffer through `mgx_xattn_fwd`'s row strides.  Padded query rows are computed like any other; only row 0 of
-a prompt is used.  Excluded keys are excluded exactly: upstream adds -10000 (transformers: finfo.min) to their scores, a weight
-that underflows to exactly 0 in fp32 and fp64 alike.
+call), residual sums ride the GEMM epilogue with a ones gate (encoder_host.py).  The image encoder is clip_vision.VitTrunk with
+its own tail; the text encoder's post-norm layer is a loop of its own on the shared helpers.  The image tokens are the same for
+every text layer, so the cross-attention keys and values of ALL layers come from ONE GEMM, weight [layers x 2 x width,
+encoder_width]; layer i reads its K and V out of that buffer through `mgx_xattn_fwd`'s row strides.  Padded query rows are
+computed like any other; only row 0 of a prompt is used.  Excluded keys are excluded exactly: upstream adds -10000
+(transformers: finfo.min) to their scores, a weight that underflows to exactly 0 in fp32 and fp64 alike.
 
 Weights: one state dict in either of two key formats, converted to one internal layout (`convert_state_dict`):
     (a) transformers' names: `vision_model.` + BlipVisionModel's keys, `text_encoder.` + BlipTextModel's keys (pinned against
@@ -29,8 +30,9 @@ from dataclasses import dataclass, replace
 import torch
 
 from . import ops
-from .clip_vision import ClipVisionConfig, ClipVisionTower
-from .ops import BF16, F32, Rows, EPI_BIAS_GATE_RES
+from .clip_vision import ClipVisionConfig, VitTrunk
+from .encoder_host import EncoderHost, convert_names, draw_state_dict, layer_norm_net_std
+from .ops import BF16, F32
 
 MEAN, STD = 0.16717362830052426, 1.0333394966054072      # recollected from upstream ImageReward (ImageReward.py), unpinned
 HEAD_WIDTHS = (1024, 128, 64, 16, 1)
@@ -192,28 +194,9 @@ def convert_state_dict(sd, vision_config, text_config):
     wrong shape, or unknown under the format's prefixes raise a ValueError that names them; `position_ids` buffers are ignored."""
     hf = not _is_upstream(sd)
     names = _hf_names(vision_config, text_config) if hf else _upstream_names(vision_config, text_config)
-    out, missing, used = {}, [], set()
-    for name, src in names.items():
-        parts = src if isinstance(src, tuple) else (src,)
-        miss = [p for p in parts if p not in sd]
-        if miss:
-            missing += miss
-            continue
-        used.update(parts)
-        t = torch.cat([sd[p] for p in parts], 0) if len(parts) > 1 else sd[parts[0]]
-        if name == "vis.cls" and t.dim() == 3 and tuple(t.shape[:2]) == (1, 1):
-            t = t[0, 0]
-        if name == "vis.pos" and t.dim() == 3 and t.shape[0] == 1:
-            t = t[0]
-        out[name] = t
-    unknown = sorted(k for k in sd if k.startswith(_PREFIXES[hf]) and k not in used and not k.endswith("position_ids"))
-    if missing or unknown:
-        raise ValueError(f"ImageReward state dict: missing {sorted(missing)[:8]} ({len(missing)}), unknown {unknown[:8]} ({len(unknown)})")
-    bad = [f"{names[k] if isinstance(names[k], str) else names[k][0] + ' ...'} -> {k} {tuple(out[k].shape)} != {shp}"
-           for k, shp in param_shapes(vision_config, text_config).items() if tuple(out[k].shape) != tuple(shp)]
-    if bad:
-        raise ValueError(f"ImageReward state dict: wrong shapes: {bad[:8]}")
-    return out
+    fixups = {"vis.cls": lambda t: t[0, 0] if t.dim() == 3 and tuple(t.shape[:2]) == (1, 1) else t,
+              "vis.pos": lambda t: t[0] if t.dim() == 3 and t.shape[0] == 1 else t}
+    return convert_names(sd, names, param_shapes(vision_config, text_config), _PREFIXES[hf], "ImageReward", fixups=fixups)
 
 
 def vision_config_from_state_dict(sd):
@@ -247,12 +230,14 @@ def load_tokenizer(path, max_length=MAX_LENGTH):
 
 
 # ------------------------------------------------------------------------------------------------------------ image encoder
-class BlipVisionEncoder(ClipVisionTower):
-    """BLIP's ViT on ClipVisionTower's buffers, preprocessing (`mgx_clip_preprocess`) and kernels.  `P`: the `vis.*` entries of
-    the internal layout, without the prefix."""
+class BlipVisionEncoder(VitTrunk):
+    """BLIP's ViT on the trunk ClipVisionTower runs: its buffers, preprocessing (`mgx_clip_preprocess`) and kernels.  `P`: the
+    `vis.*` entries of the internal layout, without the prefix.  The weights come through ImageRewardModel only, and there is no
+    projection: the tower's entry points for those refuse."""
+    label = "BLIP vision"
 
     def __init__(self, config: BlipVisionConfig = None, device="cuda"):
-        super().__init__(config or BLIP_VIT_L_16, device=device)
+        super().__init__(config or BLIP_VIT_L_16, device)
 
     @classmethod
     def from_pretrained(cls, path, device="cuda"):
@@ -267,21 +252,7 @@ class BlipVisionEncoder(ClipVisionTower):
     def load_internal(self, t):
         """The `vis.*` tensors (prefix stripped).  Matrices and biases go to bf16, LayerNorm parameters, class token and position
         embeddings stay fp32; the patch weight is flattened to [width, 3 p p], zero-padded to the GEMM's K % 64 == 0."""
-        c, dev = self.config, self.device
-        Kp = ops.clip_patch_cols(c.patch_size)
-        P = {}
-        for k, v in t.items():
-            v = v.to(dev)
-            if k == "patch.weight":
-                w = torch.zeros(c.width, Kp, dtype=BF16, device=dev)
-                w[:, :3 * c.patch_size ** 2] = v.reshape(c.width, -1).to(BF16)
-                P[k] = w
-            elif k in ("cls", "pos") or ".ln_" in k or k.startswith("ln_"):
-                P[k] = v.to(F32).contiguous()
-            else:
-                P[k] = v.to(BF16).contiguous()
-        self.P = P
-        return self
+        return self._load(t)
 
     def encode_image(self, *a, **k):
         raise NotImplementedError("BLIP's ViT has no projection: use encode_tokens")
@@ -289,61 +260,28 @@ class BlipVisionEncoder(ClipVisionTower):
     @torch.no_grad()
     def encode_tokens(self, images=None, pixel_values=None):
         """-> [B tokens, width] bf16 (a shared buffer): the final LayerNorm of every token.  Give decoded `images`
-        (ClipVisionTower.preprocess) or `pixel_values` [B, 3, R, R] already resized and normalised."""
-        if self.P is None:
-            raise RuntimeError("BLIP vision weights not loaded")
-        if (images is None) == (pixel_values is None):
-            raise ValueError("give images or pixel_values")
-        c, P = self.config, self.P
-        patches = self.preprocess(images) if pixel_values is None else self._patchify(pixel_values)
-        w, S, H, d, mlp, eps = c.width, c.tokens, c.heads, c.head_dim, c.mlp_width, c.layer_norm_eps
-        B = patches.shape[0] // (S - 1)
-        M = B * S
-        gemm = lambda a, W, b, out, N, K, **kw: ops.gemm(Rows.of(a), W, b, Rows.of(out), N, K, stream_k=False, **kw)
-        pe = self._plain("patch_out", B * (S - 1), w)
-        gemm(patches, P["patch.weight"], P["patch.bias"], pe, w, patches.shape[1])
-        x = self._plain("x", M, w)
-        ops.vit_embed(pe, P["cls"], P["pos"], x, B, S, w)
-        n, qkv, o, h = self._plain("n", M, w), self._plain("qkv", M, 3 * w), self._plain("o", M, w), self._plain("h", M, mlp)
-        for i in range(c.layers):
-            L = f"layers.{i}."
-            ops.layer_norm_affine(x, w, P[L + "ln_1.weight"], P[L + "ln_1.bias"], n, w, M, w, eps)
-            gemm(n, P[L + "qkv.weight"], P[L + "qkv.bias"], qkv, 3 * w, w)
-            if not ops.vit_attn_fwd(qkv, 3 * w, o, w, B, H, S, d, d ** -0.5):
-                raise RuntimeError(f"mgx_vit_attn_fwd refused {S} tokens")
-            gemm(o, P[L + "out.weight"], P[L + "out.bias"], x, w, w, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
-            ops.layer_norm_affine(x, w, P[L + "ln_2.weight"], P[L + "ln_2.bias"], n, w, M, w, eps)
-            gemm(n, P[L + "fc1.weight"], P[L + "fc1.bias"], h, mlp, w)
-            ops.act_rows(h, mlp, h, mlp, M, mlp, ops.ACT_GELU)
-            gemm(h, P[L + "fc2.weight"], P[L + "fc2.bias"], x, w, mlp, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
-        tokens = self._plain("tokens", M, w)
-        ops.layer_norm_affine(x, w, P["ln_post.weight"], P["ln_post.bias"], tokens, w, M, w, eps)
+        (VitTrunk.preprocess) or `pixel_values` [B, 3, R, R] already resized and normalised."""
+        x, B = self._trunk(images, pixel_values, ops.ACT_GELU)
+        c = self.config
+        tokens = self._plain("tokens", B * c.tokens, c.width)
+        self._layer_norm(x, "ln_post", tokens, B * c.tokens, c.width, c.layer_norm_eps)
         return tokens
 
 
 # ------------------------------------------------------------------------------------------------------------- text encoder
-class BlipTextEncoder:
+class BlipTextEncoder(EncoderHost):
     """BERT with a cross-attention sub-layer in every layer.  `P`: the `txt.*` entries of the internal layout, without the
     prefix."""
 
     def __init__(self, config: BertXattnConfig = None, device="cuda"):
         self.config = (config or BERT_BASE_XATTN).check()
-        self.device = torch.device(device)
-        self.P = None
-        self._buf = {}
-        self._ones = torch.ones(max(self.config.width, 512), dtype=BF16, device=self.device)
+        super().__init__(device, self.config.width)
         self.launches = 0                   # kernel launches of the last `encode` (the rows are few: the encoder is latency-bound)
 
     def load_internal(self, t):
         """Matrices, biases and the word table go to bf16, LayerNorm parameters and position embeddings stay fp32."""
-        P = {}
-        for k, v in t.items():
-            fp32 = k == "pos" or ".ln_" in k or k.startswith("ln_")
-            P[k] = v.to(self.device).to(F32 if fp32 else BF16).contiguous()
-        self.P = P
+        self.P = self._place(t)
         return self
-
-    _plain = ClipVisionTower._plain
 
     @torch.no_grad()
     def encode(self, input_ids, lengths, image_tokens):
@@ -364,13 +302,13 @@ class BlipTextEncoder:
         M = B * S
         count = [0]
 
-        def gemm(a, W, b, out, N, K, **kw):
+        def linear(a, name, out, residual=False):
             count[0] += 1
-            ops.gemm(Rows.of(a), W, b, Rows.of(out), N, K, stream_k=False, **kw)
+            self._linear(a, name, out, residual)
 
         def norm(name):
             count[0] += 1
-            ops.layer_norm_affine(x, w, P[name + ".weight"], P[name + ".bias"], x, w, M, w, eps)
+            self._layer_norm(x, name, x, M, w, eps)
 
         def attend(*a, **kw):
             count[0] += 1
@@ -385,23 +323,23 @@ class BlipTextEncoder:
         norm("ln_emb")
         ldkv = c.layers * 2 * w
         kv = self._plain("xkv", B * T, ldkv)
-        gemm(image_tokens, P["xkv.weight"], P["xkv.bias"], kv, ldkv, e)
+        linear(image_tokens, "xkv", kv)
         lens = lengths.to(device=self.device, dtype=torch.int32)
         for i in range(c.layers):
             L = f"layers.{i}."
-            gemm(x, P[L + "qkv.weight"], P[L + "qkv.bias"], qkv, 3 * w, w)
+            linear(x, L + "qkv", qkv)
             attend(qkv, 3 * w, qkv[:, w:], 3 * w, qkv[:, 2 * w:], 3 * w, o, w, B, H, S, S, d, d ** -0.5, kv_len=lens,
                    kv_len_checked=True)
-            gemm(o, P[L + "out.weight"], P[L + "out.bias"], x, w, w, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
+            linear(o, L + "out", x, residual=True)
             norm(L + "ln_attn")
-            gemm(x, P[L + "xq.weight"], P[L + "xq.bias"], q, w, w)
+            linear(x, L + "xq", q)
             attend(q, w, kv[:, 2 * w * i:], ldkv, kv[:, 2 * w * i + w:], ldkv, o, w, B, H, S, T, d, d ** -0.5)
-            gemm(o, P[L + "xout.weight"], P[L + "xout.bias"], x, w, w, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
+            linear(o, L + "xout", x, residual=True)
             norm(L + "ln_x")
-            gemm(x, P[L + "fc1.weight"], P[L + "fc1.bias"], h, mlp, w)
+            linear(x, L + "fc1", h)
             ops.act_rows(h, mlp, h, mlp, M, mlp, ops.ACT_GELU)
             count[0] += 1
-            gemm(h, P[L + "fc2.weight"], P[L + "fc2.bias"], x, w, mlp, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
+            linear(h, L + "fc2", x, residual=True)
             norm(L + "ln_out")
         self.launches = count[0]
         return x
@@ -412,7 +350,7 @@ def _split(t, prefix):
     return {k[len(prefix):]: v for k, v in t.items() if k.startswith(prefix)}
 
 
-class ImageRewardModel:
+class ImageRewardModel(EncoderHost):
     """`(images, prompts) -> list[float]`, the order reward_adapter.compute_reward uses; all pairs of a call run as one batch.
     Images are [3, H, W] device tensors as AutoencoderKL.decode returns them (PIL images take ClipVisionTower's host path).
     `tokenizer`: a callable `prompts -> (input_ids [n, 35], lengths [n])` or a tokenizer directory (`load_tokenizer`, on first
@@ -423,12 +361,11 @@ class ImageRewardModel:
         self.text = BlipTextEncoder(text_config or replace(BERT_BASE_XATTN, encoder_width=self.vision.config.width), device=device)
         if self.text.config.encoder_width != self.vision.config.width:
             raise ValueError(f"encoder_width {self.text.config.encoder_width} is not the image encoder's width {self.vision.config.width}")
-        self.device = self.vision.device
+        super().__init__(self.vision.device)
         self.tokenizer, self.mean, self.std = tokenizer, float(mean), float(std)
         if self.std == 0.0:
             raise ValueError("std must not be 0")
         self.head = None
-        self._buf = {}
 
     # ---------------------------------------------------------------------------------------------- weights
     @classmethod
@@ -458,18 +395,7 @@ class ImageRewardModel:
         """Random weights of the configured architecture drawn on the model's device, transformers' key names."""
         return self.load_state_dict(synthetic_state_dict(self.vision.config, self.text.config, seed, self.device))
 
-    def to(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag=False):
-        return self
-
     # ---------------------------------------------------------------------------------------------- forward
-    _plain = ClipVisionTower._plain
-
     def tokenize(self, prompts):
         if self.tokenizer is None:
             raise ValueError("ImageRewardModel needs a tokenizer: a callable prompts -> (ids, lengths) or a tokenizer directory")
@@ -514,26 +440,11 @@ def synthetic_state_dict(vision_config, text_config, seed=0, device="cpu"):
     """A random state dict of the two configurations in transformers' names (format (a)), drawn on `device`, every value a bf16
     number held in fp32.  The text encoder's query weights are drawn four times as large as fan-in scaling would, so that the
     attention is not nearly uniform."""
-    g = torch.Generator(device=device).manual_seed(seed)
-    r = lambda shp, std: (std * torch.randn(shp, generator=g, device=device)).to(BF16).float()
-    shapes = param_shapes(vision_config, text_config)
-    sd = {}
-    for name, src in _hf_names(vision_config, text_config).items():
-        shp = shapes[name]
-        parts = src if isinstance(src, tuple) else (src,)
-        for key in parts:
-            s = (shp[0] // len(parts),) + tuple(shp[1:])
-            if name in ("vis.cls", "vis.pos", "txt.tok", "txt.pos"):
-                t = r(s, 0.5)
-                sd[key] = t.view((1, 1) + s) if name == "vis.cls" else t.view((1,) + s) if name == "vis.pos" else t
-            elif name.endswith("weight") and len(shp) == 1:
-                sd[key] = (1.0 + 0.1 * torch.randn(s, generator=g, device=device)).to(BF16).float()
-            elif name.endswith("bias"):
-                sd[key] = r(s, 0.05)
-            else:
-                fan_in = 1
-                for v in s[1:]:
-                    fan_in *= v
-                boost = 4.0 if key.endswith("self.query.weight") else 1.0
-                sd[key] = r(s, boost * fan_in ** -0.5)
+    def std(name, key, s):
+        sigma = layer_norm_net_std(name, key, s)
+        return 4.0 * sigma if key.endswith("self.query.weight") else sigma
+    names = _hf_names(vision_config, text_config)
+    sd = draw_state_dict(names, param_shapes(vision_config, text_config), std, seed, device)
+    for name, lead in (("vis.cls", (1, 1)), ("vis.pos", (1,))):     # transformers keeps them [1, 1, w] and [1, S, w]
+        sd[names[name]] = sd[names[name]].view(lead + tuple(sd[names[name]].shape))
     return sd

@@ -5,8 +5,9 @@ Inference only.
 Layout, as clip_vision.py: all prompts of a call are one batch of M = B S token rows, bf16; every Linear (none has a bias) is a
 launch of the persistent GEMM (`ops.gemm(..., stream_k=False)`: a prompt's rows do not depend on how many prompts share the
 call), q | k | v and wi_0 | wi_1 each as one fused GEMM, residual sums in the `o` and `wo` GEMMs' epilogue with a ones gate.
-csrc/text.hip holds the rest: the embedding gather, T5LayerNorm (`mgx_rms_norm_affine`), the attention with the relative-position
-bias as a compact [H, 2 S - 1] table (`mgx_text_attn_fwd`; the bias depends on (head, k - q) only) and the gated tanh GELU.
+csrc/text.hip holds the rest: the embedding gather, T5LayerNorm (`mgx_rms_norm_affine`) and the gated tanh GELU; the attention
+takes the relative-position bias as a compact [H, 2 S - 1] table (`mgx_text_attn_fwd`, csrc/encoder_attn.hip; the bias depends on
+(head, k - q) only).  The layer is encoder_host.py's pre-norm walk, with T5's norm, attention, activation and Linear names.
 
 No attention mask: FLUX's `encode_prompt` passes none to T5, so the padding tokens of a prompt are attended like any other.
 `encode` has no `attention_mask` argument that works: giving one raises.
@@ -15,15 +16,14 @@ Stated deviation: transformers' T5LayerNorm under bf16 rounds twice (after the n
 `mgx_rms_norm_affine` rounds once.
 
 Key names are transformers' `T5EncoderModel` names, pinned against it by tests/test_text_refs.py."""
-import json
 import math
-import os
 from dataclasses import dataclass, replace
 
 import torch
 
 from . import ops
-from .ops import BF16, F32, Rows, EPI_BIAS_GATE_RES
+from .encoder_host import EncoderHost, convert_names, draw_state_dict, read_checkpoint_dir
+from .ops import BF16, F32
 
 
 @dataclass
@@ -111,30 +111,7 @@ def convert_state_dict(sd, config):
     """A T5EncoderModel state dict -> the internal dict.  q | k | v and wi_0 | wi_1 are fused along dim 0.  Missing, unknown
     (`shared.` / `encoder.` keys the layout does not know) and wrongly shaped tensors raise a ValueError that names them; keys
     of other networks are ignored."""
-    out, missing, used = {}, [], set()
-    for name, src in _hf_names(config).items():
-        if isinstance(src, list):
-            have = [p for p in src if p in sd]
-            if not have:
-                missing.append(src[0])
-                continue
-            used.update(have)
-            out[name] = sd[have[0]]
-            continue
-        parts = src if isinstance(src, tuple) else (src,)
-        miss = [p for p in parts if p not in sd]
-        if miss:
-            missing += miss
-            continue
-        used.update(parts)
-        out[name] = torch.cat([sd[p] for p in parts], 0) if len(parts) > 1 else sd[parts[0]]
-    unknown = sorted(k for k in sd if k.startswith(("shared.", "encoder.")) and k not in used)
-    if missing or unknown:
-        raise ValueError(f"T5 encoder state dict: missing {sorted(missing)[:8]} ({len(missing)}), unknown {unknown[:8]} ({len(unknown)})")
-    bad = [f"{k} {tuple(out[k].shape)} != {shp}" for k, shp in param_shapes(config).items() if tuple(out[k].shape) != tuple(shp)]
-    if bad:
-        raise ValueError(f"T5 encoder state dict: wrong shapes: {bad[:8]}")
-    return out
+    return convert_names(sd, _hf_names(config), param_shapes(config), ("shared.", "encoder."), "T5 encoder")
 
 
 def config_from_json(raw):
@@ -150,55 +127,31 @@ def config_from_json(raw):
                            max_distance=raw.get("relative_attention_max_distance", 128), eps=raw.get("layer_norm_epsilon", 1e-6))
 
 
-class T5Encoder:
+class T5Encoder(EncoderHost):
     def __init__(self, config: T5EncoderConfig = None, device="cuda"):
         self.config = (config or T5_XXL).check()
-        self.device = torch.device(device)
-        self.P = None
-        self._buf = {}
+        super().__init__(device, self.config.d_model)
         self._tables = {}
-        self._ones = torch.ones(max(self.config.d_model, 512), dtype=BF16, device=self.device)
 
     # ---------------------------------------------------------------------------------------------- weights
     @classmethod
     def from_pretrained(cls, path, device="cuda"):
         """A directory with `config.json` (see `config_from_json`) and one or more `*.safetensors` files."""
-        from .clip_text import _read_dir
-        raw, sd = _read_dir(path)
+        raw, sd = read_checkpoint_dir(path)
         return cls(config_from_json(raw), device=device).load_state_dict(sd)
-
-    def to(self, *a, **k):
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag=False):
-        return self
 
     def load_state_dict(self, sd):
         """Matrices and the token table go to bf16 on the device, the norm weights to fp32 there; the relative-attention weight
         stays on the host in fp32 (the bias table is built there, once per sequence length)."""
-        P = {}
-        for k, v in convert_state_dict(sd, self.config).items():
-            if k == "rel_bias":
-                P[k] = v.detach().to("cpu", F32).contiguous()
-            else:
-                P[k] = v.to(self.device).to(F32 if ".ln_" in k or k.startswith("ln_") else BF16).contiguous()
-        self.P, self._tables = P, {}
+        t = convert_state_dict(sd, self.config)
+        rel_bias = t.pop("rel_bias")
+        self.P, self._tables = self._place(t), {}
+        self.P["rel_bias"] = rel_bias.detach().to("cpu", F32).contiguous()
         return self
 
     def init_synthetic(self, seed=0):
         """Random weights of the configured architecture drawn on the encoder's device, every value a bf16 number."""
         return self.load_state_dict(synthetic_state_dict(self.config, seed, self.device))
-
-    # ---------------------------------------------------------------------------------------------- buffers
-    def _plain(self, tag, M, C, dtype=BF16):
-        key = (tag, M, C, dtype)
-        t = self._buf.get(key)
-        if t is None:
-            t = self._buf[key] = torch.empty(M, C, dtype=dtype, device=self.device)
-        return t
 
     def bias_table(self, S):
         """[H, 2 S - 1] fp32 on the device: from block 0's weight, for every layer; built on the host once per S"""
@@ -223,49 +176,39 @@ class T5Encoder:
         B, S = input_ids.shape
         D, H, d, inner, ff, eps = c.d_model, c.heads, c.d_kv, c.inner, c.d_ff, c.eps
         M = B * S
-        gemm = lambda a, W, out, N, K, **kw: ops.gemm(Rows.of(a), W, None, Rows.of(out), N, K, stream_k=False, **kw)
         x = self._plain("x", M, D)
         ops.token_embed(input_ids, P["tok"], None, x)           # checks the ids on the host first: nothing launched on a bad one
         table = self.bias_table(S)
         n, qkv, o = self._plain("n", M, D), self._plain("qkv", M, 3 * inner), self._plain("o", M, inner)
         h, a = self._plain("h", M, 2 * ff), self._plain("a", M, ff)
-        for i in range(c.layers):
-            L = f"layers.{i}."
-            ops.rms_norm_affine(x, D, P[L + "ln_1.weight"], n, D, M, D, eps)
-            gemm(n, P[L + "qkv.weight"], qkv, 3 * inner, D)
+
+        def norm(src, name, dst):                               # T5LayerNorm: no mean, no bias, one rounding
+            ops.rms_norm_affine(src, D, P[name + ".weight"], dst, D, M, D, eps)
+
+        def attend(qkv, o):                                     # scale 1: T5 does not scale q.k
             if not ops.text_attn_fwd(qkv, 3 * inner, o, inner, B, H, S, d, 1.0, causal=False, rel_bias=table):
                 raise RuntimeError(f"mgx_text_attn_fwd refused {S} tokens")
-            gemm(o, P[L + "o.weight"], x, D, inner, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
-            ops.rms_norm_affine(x, D, P[L + "ln_2.weight"], n, D, M, D, eps)
-            gemm(n, P[L + "wi.weight"], h, 2 * ff, D)
+
+        def activate(h):                                        # gelu(wi_0 x) * wi_1 x: the two halves of h's rows -> a
             ops.gated_act_rows(h, 2 * ff, h[:, ff:], 2 * ff, a, ff, M, ff, ops.ACT_GELU_TANH)
-            gemm(a, P[L + "wo.weight"], x, D, ff, epi=EPI_BIAS_GATE_RES, gate=self._ones, gate_ld=0)
+            return a
+
+        for i in range(c.layers):
+            self._prenorm_layer(f"layers.{i}.", x, n, qkv, o, h, norm, attend, activate, ("qkv", "o", "wi", "wo"))
         out = torch.empty(B, S, D, dtype=BF16, device=self.device)
-        ops.rms_norm_affine(x, D, P["ln_final.weight"], out, D, M, D, eps)
+        norm(x, "ln_final", out)
         return out
 
 
 def synthetic_state_dict(config, seed=0, device="cpu"):
     """A random T5EncoderModel-named state dict of `config`, drawn on `device`, every value a bf16 number held in fp32.  The
     scales keep the residual stream of order 1: T5 has no bias and no mean subtraction to rein it in."""
-    g = torch.Generator(device=device).manual_seed(seed)
-    r = lambda shp, std: (std * torch.randn(shp, generator=g, device=device)).to(BF16).float()
-    sd = {}
-    shapes = param_shapes(config)
-    for name, src in _hf_names(config).items():
-        shp = shapes[name]
-        keys = src if isinstance(src, (tuple, list)) else (src,)
-        first = None
-        for key in keys:
-            s = (shp[0] // len(src),) + tuple(shp[1:]) if isinstance(src, tuple) else shp
-            if isinstance(src, list):                            # the tied table: one tensor under both names
-                first = sd[key] = r(s, 1.0) if first is None else first
-            elif name == "rel_bias":
-                sd[key] = r(s, 1.0)
-            elif len(shp) == 1:
-                sd[key] = (1.0 + 0.1 * torch.randn(s, generator=g, device=device)).to(BF16).float()
-            elif key.endswith("SelfAttention.q.weight"):         # T5 does not scale q.k by d_kv^-0.5: its initialisation does
-                sd[key] = r(s, (s[1] * config.d_kv) ** -0.5)
-            else:
-                sd[key] = r(s, s[1] ** -0.5)
-    return sd
+    def std(name, key, s):
+        if name in ("tok", "rel_bias"):
+            return 1.0
+        if len(s) == 1:
+            return None
+        if key.endswith("SelfAttention.q.weight"):               # T5 does not scale q.k by d_kv^-0.5: its initialisation does
+            return (s[1] * config.d_kv) ** -0.5
+        return s[1] ** -0.5
+    return draw_state_dict(_hf_names(config), param_shapes(config), std, seed, device)

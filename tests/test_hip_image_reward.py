@@ -110,9 +110,9 @@ def test_xattn_fwd(B, H, Sq, Skv, d, arm):
 
 @pytest.mark.parametrize("B,H,S,d", [(2, 3, 17, 64), (1, 2, 130, 80), (2, 12, 35, 64)])
 def test_xattn_fwd_packed(B, H, S, d):
-    """q, k and v pointing into one packed q | k | v buffer, Sq == Skv, no lengths: the problem of mgx_vit_attn_fwd.  The body
-    is a sibling of that kernel's with the same operations in the same order, so beyond the float64 budget the two agree bit
-    for bit."""
+    """q, k and v pointing into one packed q | k | v buffer, Sq == Skv, no lengths: the problem of mgx_vit_attn_fwd.  Both
+    entry points launch the same kernel instance (csrc/encoder_attn.hip), so beyond the float64 budget the two agree bit for
+    bit."""
     ops = _ops()
     w = H * d
     qkv = torch.randn(B * S, 3 * w, device="cuda", generator=_g(S + d)).to(BF)
