@@ -59,6 +59,81 @@ def sentinel(shape, device="cuda"):
     return (torch.arange(math.prod(shape), device=device) % 251 + 1).to(torch.int16).view(torch.bfloat16).view(shape)
 
 
+# ---- the exact GEMM tests (test_hip_gemm_handover.py, test_hip_gemm_small.py): operands on a grid whose sums are exact in fp32
+GCOLS, GROWS = 8, 3  # guard columns right of every row, guard rows below every batch
+
+
+def grid_ints(shape, lo, hi, div, gen):
+    """randint(lo .. hi inclusive) / div as bf16, on the CPU"""
+    import torch
+    return (torch.randint(lo, hi + 1, shape, generator=gen).float() / div).bfloat16()
+
+
+def exact_gemm_problem(Mr, Nr, K):
+    """(A [Mr, K], W [Nr, K], bias [Nr], acc = A @ W^T in fp32 -- exact) on the CPU: A in multiples of 1/8 up to 1/2, W in
+    multiples of 1/4 up to 1/2, so every product and partial sum is a multiple of 1/32 below 2^24 / 32 (asserted)."""
+    import torch
+    g = torch.Generator().manual_seed(Mr + 3 * Nr + K)
+    A = grid_ints((Mr, K), -4, 4, 8, g)
+    W = grid_ints((Nr, K), -2, 2, 4, g)
+    bias = grid_ints((Nr,), -16, 16, 32, g)
+    acc = A.float() @ W.float().t()
+    assert float(acc.abs().max()) * 32 < 2 ** 24
+    return A, W, bias, acc
+
+
+class GuardedOut:
+    """A row-batched (or plain: rpb None) output matrix with guard rows and columns, and the bookkeeping to check them."""
+
+    def __init__(self, Mr, N, rpb, dtype, gen):
+        import torch
+        from mixgrpo_amd.ops import Rows
+        self.M, self.N, self.rpb = Mr, N, rpb or Mr
+        self.ld = N + GCOLS
+        nb = (Mr + self.rpb - 1) // self.rpb
+        cg = torch.Generator(device="cuda").manual_seed(int(torch.randint(0, 2 ** 31, (1,), generator=gen)))
+        self.init = (torch.randint(-64, 65, (nb, self.rpb + GROWS, self.ld), generator=cg, device="cuda").float() / 32).to(dtype)
+        self.store = self.init.clone()
+        self.rows = Rows(self.store, Mr, self.ld, self.rpb if rpb else 1 << 40, (self.rpb + GROWS) * self.ld if rpb else 0)
+        bi, ri = torch.arange(nb)[:, None], torch.arange(self.rpb + GROWS)[None, :]
+        row_ok = (ri < self.rpb) & (bi * self.rpb + ri < Mr)                  # [batch, row]: a row of the matrix
+        owned = row_ok[:, :, None] & (torch.arange(self.ld) < N)[None, None, :]
+        self.guard = (~owned).cuda()
+
+    def dense(self, t=None):
+        t = self.store if t is None else t
+        return t[:, :self.rpb, :self.N].reshape(-1, self.N)[:self.M]
+
+    def reset(self):
+        self.store.copy_(self.init)
+
+    def guards_untouched(self):
+        import torch
+        return torch.equal(self.store[self.guard], self.init[self.guard])
+
+    def batch_of_row(self):
+        import torch
+        return torch.arange(self.M) // self.rpb
+
+
+def same_bits(got, want):
+    """bit-for-bit on the CPU (bf16 / fp32 compared as integers: -0.0 != 0.0, and a NaN cannot hide)"""
+    import torch
+    it = torch.int16 if got.dtype == torch.bfloat16 else torch.int32
+    got, want = got.cpu().contiguous(), want.cpu().contiguous()
+    assert got.dtype == want.dtype and got.shape == want.shape
+    same = torch.equal(got.view(it), want.view(it))
+    if not same:
+        bad = (got.view(it) != want.view(it)).nonzero()
+        raise AssertionError(f"{bad.shape[0]} elements differ, first at {bad[0].tolist()}: got {got[tuple(bad[0])].item()} "
+                             f"want {want[tuple(bad[0])].item()}")
+
+
+def linear_ref(acc, bias, N, with_bias):
+    """bf16(acc + bias): the Linear's output"""
+    return (acc[:, :N] + bias[:N].float()).bfloat16() if with_bias else acc[:, :N].bfloat16()
+
+
 def oracle_flux(cfg, P, device=None):
     """oracle/mmdit.forward behind the transformer call signature, parameters trainable (fp32 master weights; the
     restatement rounds to bf16 where autocast does).  Used by the end-to-end tests on both the CPU and the GPU side.

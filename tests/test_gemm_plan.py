@@ -10,6 +10,7 @@ import math
 import pytest
 
 from test_hip_gemm import BIG, SK_SHAPES, SMALL
+from test_hip_gemm_small import ROWS_FULL, ROWS_RANGES, SHAPES as SMALL_EXACT
 
 SK_F32_SHAPES = [(2048, 4096, 8192 + 64), (3072, 12288, 4096 + 64), (6144, 3072, 4096)]       # test_gemm_stream_k_f32_accumulate
 
@@ -92,7 +93,7 @@ def test_stream_k_rule_splits_the_test_shapes():
     assert not any(_lib_splits(3072, 3072, 28672))       # R = 18 likewise
 
 
-WALKED = SK_SHAPES + SK_F32_SHAPES + BIG + [(4608, 3072, 15360), (3072, 3072, 28672), (36864, 3072, 3072)] + SMALL
+WALKED = SK_SHAPES + SK_F32_SHAPES + BIG + [(4608, 3072, 15360), (3072, 3072, 28672), (36864, 3072, 3072)] + SMALL + SMALL_EXACT
 
 
 @pytest.mark.parametrize("sk", [False, True])
@@ -147,6 +148,25 @@ def test_family_predicate():
         assert _plan(*shp, True)["family"] == 0, shp
     for shp in SK_SHAPES + SK_F32_SHAPES:
         assert _plan(*shp, True)["family"] == 1, shp
+
+
+@pytest.mark.parametrize("M,N,K", SMALL_EXACT)
+def test_exact_shapes_of_the_128x128_kernel_are_family_0(M, N, K):
+    """The shapes of test_hip_gemm_small.py go to the 128x128 kernel, workspace or not, one workgroup per 128x128 tile in bands
+    of SMALL_BAND tile rows -- otherwise they would silently test the other kernel."""
+    for sk in (False, True):
+        p = _plan(M, N, K, sk)
+        assert (p["family"], p["grid"], p["band"], p["nfix"]) == (0, math.ceil(M / 128) * math.ceil(N / 128), 8, 0), (M, N, K, p)
+
+
+def test_row_ranges_change_kernel_family():
+    """test_rows_do_not_depend_on_m_or_kernel: the full problem is the persistent kernel's (128 tiles, nothing split without a
+    workspace), every row range of it the 128x128 kernel's."""
+    M, N, K = ROWS_FULL
+    p = _plan(M, N, K, False)
+    assert p["family"] == 1 and p["nfix"] == 0 and math.ceil(M / 256) * math.ceil(N / 256) == 128
+    for r0, rows in ROWS_RANGES:
+        assert r0 + rows <= M and _plan(rows, N, K, False)["family"] == 0, (r0, rows)
 
 
 def test_band_rule():

@@ -41,6 +41,10 @@ def _ops():
 
 # -------------------------------------------------------------------------------------------------------------- attention
 ATTN = [(1, 1, 1, 64), (2, 3, 17, 80), (1, 2, 64, 64), (1, 2, 65, 80), (2, 16, 257, 80), (1, 4, 577, 64)]
+# every instance of the dispatch (csrc/encoder_attn.hip): DP = 32 exact and padded (d = 32, 16), 64 padded (48), 96 exact, 128
+# padded and exact (112, 128), at one key and at 70 (two query blocks, two key blocks, the second with 6 keys)
+HEAD_DIMS = [16, 32, 48, 96, 112, 128]
+ATTN += [(2, 3, S, d) for d in HEAD_DIMS for S in (1, 70)]
 GUARD = 8                                              # guard columns left and right of both buffers (16 bytes)
 
 

@@ -14,6 +14,9 @@ import functools
 import pytest
 import torch
 
+from helpers import GCOLS, exact_gemm_problem
+from helpers import GuardedOut as _Out, grid_ints as _ints, linear_ref as _y_ref, same_bits as _same_bits
+
 pytestmark = pytest.mark.gpu
 
 EPI_BIAS, EPI_GELU, EPI_GATE_RES, EPI_F32_ACC, EPI_DGELU = 0, 1, 2, 3, 4
@@ -22,71 +25,12 @@ NMAX = 8200
 KS = [128, 192, 320]
 NS = [8192, 8200, 8196]
 RPB = 1152           # 9 x 128 rows per batch of C: tiles cross batch boundaries, a wave's 128 rows do not (the 16-byte paths' condition)
-GCOLS, GROWS = 8, 3  # guard columns right of every row, guard rows below every batch
-
-
-def _ints(shape, lo, hi, div, gen):
-    return (torch.randint(lo, hi + 1, shape, generator=gen).float() / div).bfloat16()
 
 
 @functools.lru_cache(maxsize=4)
 def _problem(Mr, Nr, K):
-    """(A [Mr, K], W [Nr, K], bias [Nr], acc = A @ W^T in fp32 -- exact) on the CPU; computed once per shape and never modified."""
-    g = torch.Generator().manual_seed(Mr + 3 * Nr + K)
-    A = _ints((Mr, K), -4, 4, 8, g)
-    W = _ints((Nr, K), -2, 2, 4, g)
-    bias = _ints((Nr,), -16, 16, 32, g)
-    acc = A.float() @ W.float().t()
-    assert float(acc.abs().max()) * 32 < 2 ** 24
-    return A, W, bias, acc
-
-
-class _Out:
-    """A row-batched (or plain: rpb None) output matrix with guard rows and columns, and the bookkeeping to check them."""
-
-    def __init__(self, Mr, N, rpb, dtype, gen):
-        from mixgrpo_amd.ops import Rows
-        self.M, self.N, self.rpb = Mr, N, rpb or Mr
-        self.ld = N + GCOLS
-        nb = (Mr + self.rpb - 1) // self.rpb
-        cg = torch.Generator(device="cuda").manual_seed(int(torch.randint(0, 2 ** 31, (1,), generator=gen)))
-        self.init = (torch.randint(-64, 65, (nb, self.rpb + GROWS, self.ld), generator=cg, device="cuda").float() / 32).to(dtype)
-        self.store = self.init.clone()
-        self.rows = Rows(self.store, Mr, self.ld, self.rpb if rpb else 1 << 40, (self.rpb + GROWS) * self.ld if rpb else 0)
-        bi, ri = torch.arange(nb)[:, None], torch.arange(self.rpb + GROWS)[None, :]
-        row_ok = (ri < self.rpb) & (bi * self.rpb + ri < Mr)                  # [batch, row]: a row of the matrix
-        owned = row_ok[:, :, None] & (torch.arange(self.ld) < N)[None, None, :]
-        self.guard = (~owned).cuda()
-
-    def dense(self, t=None):
-        t = self.store if t is None else t
-        return t[:, :self.rpb, :self.N].reshape(-1, self.N)[:self.M]
-
-    def reset(self):
-        self.store.copy_(self.init)
-
-    def guards_untouched(self):
-        return torch.equal(self.store[self.guard], self.init[self.guard])
-
-    def batch_of_row(self):
-        return torch.arange(self.M) // self.rpb
-
-
-def _same_bits(got, want):
-    """bit-for-bit on the CPU (bf16 / fp32 compared as integers: -0.0 != 0.0, and a NaN cannot hide)"""
-    it = torch.int16 if got.dtype == torch.bfloat16 else torch.int32
-    got, want = got.cpu().contiguous(), want.contiguous()
-    assert got.dtype == want.dtype and got.shape == want.shape
-    same = torch.equal(got.view(it), want.view(it))
-    if not same:
-        bad = (got.view(it) != want.view(it)).nonzero()
-        raise AssertionError(f"{bad.shape[0]} elements differ, first at {bad[0].tolist()}: got {got[tuple(bad[0])].item()} "
-                             f"want {want[tuple(bad[0])].item()}")
-
-
-def _y_ref(acc, bias, N, with_bias):
-    """bf16(acc + bias): the Linear's output"""
-    return (acc[:, :N] + bias[:N].float()).bfloat16() if with_bias else acc[:, :N].bfloat16()
+    """helpers.exact_gemm_problem, computed once per shape and never modified."""
+    return exact_gemm_problem(Mr, Nr, K)
 
 
 @pytest.mark.parametrize("N", NS)

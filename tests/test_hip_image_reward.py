@@ -44,6 +44,10 @@ def _ops():
 # -------------------------------------------------------------------------------------------------------------- attention
 XATTN = [(1, 1, 1, 1, 64), (2, 3, 5, 17, 64), (2, 12, 35, 35, 64), (1, 2, 35, 197, 64), (1, 2, 64, 65, 64), (1, 2, 65, 64, 80),
          (1, 4, 130, 300, 128)]
+# every DP of the dispatch (csrc/encoder_attn.hip): 32 exact and padded (d = 32, 16), 64 padded (48), 96 exact, 128 padded and
+# exact (112, 128); 5 queries against two key blocks (the second with 6 keys), and two query blocks against 5 keys
+HEAD_DIMS = [16, 32, 48, 96, 112, 128]
+XATTN += [(2, 3, Sq, Skv, d) for d in HEAD_DIMS for Sq, Skv in ((5, 70), (70, 5))]
 GUARD = 8                                              # guard columns left and right of every buffer (16 bytes)
 
 
@@ -108,7 +112,7 @@ def test_xattn_fwd(B, H, Sq, Skv, d, arm):
             assert not A.rows_close(out, BR.xattention(qh, kh, vh, scale, off), budget, A.C["O"])[0]
 
 
-@pytest.mark.parametrize("B,H,S,d", [(2, 3, 17, 64), (1, 2, 130, 80), (2, 12, 35, 64)])
+@pytest.mark.parametrize("B,H,S,d", [(2, 3, 17, 64), (1, 2, 130, 80), (2, 12, 35, 64), (2, 3, 70, 16), (2, 3, 70, 128)])
 def test_xattn_fwd_packed(B, H, S, d):
     """q, k and v pointing into one packed q | k | v buffer, Sq == Skv, no lengths: the problem of mgx_vit_attn_fwd.  Both
     entry points launch the same kernel instance (csrc/encoder_attn.hip), so beyond the float64 budget the two agree bit for

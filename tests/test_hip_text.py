@@ -43,17 +43,23 @@ def _ops():
 # -------------------------------------------------------------------------------------------------------------- attention
 ATTN = [(1, 1, 1, 64), (2, 3, 17, 64), (1, 2, 64, 64), (1, 2, 65, 64), (2, 12, 77, 64), (1, 2, 130, 80), (1, 4, 512, 64)]
 GUARD = 8                                              # guard columns left and right of both buffers (16 bytes)
+# every instance of the dispatch (csrc/encoder_attn.hip): DP = 32 exact and padded (d = 32, 16), 64 padded (48), 96 exact, 128
+# padded and exact (112, 128), at one key and at 70 (two query blocks, two key blocks, the second with 6 keys, a diagonal block
+# for the causal arm); `both` (mask and table at once) once per DP
+HEAD_DIMS = [16, 32, 48, 96, 112, 128]
+ATTN_ARMS = [shape + (arm,) for shape in ATTN + [(2, 3, S, d) for d in HEAD_DIMS for S in (1, 70)] for arm in ("causal", "bias", "plain")]
+ATTN_ARMS += [(2, 3, 70, d, "both") for d in (16, 48, 96, 112)]
 
 
-@pytest.mark.parametrize("arm", ["causal", "bias", "plain"])
-@pytest.mark.parametrize("B,H,S,d", ATTN)
+@pytest.mark.parametrize("B,H,S,d,arm", ATTN_ARMS)
 def test_text_attn_fwd(B, H, S, d, arm):
     """O against float64 softmax attention (mask and bias inside the scores) on the same bf16 operands, every row within the
     budget of tests/attn_refs.py for O.  The construction is test_vit_attn_fwd's: q | k | v sit inside a buffer whose guard row
     above and below and guard columns left and right hold inf / NaN; O likewise: nothing may leak in, and the guards come back
     bit for bit.  The bias table is drawn with standard deviation 2, so that it matters.  `plain` (no mask, no table) must
     equal mgx_vit_attn_fwd bit for bit.  Power: the causal arm rejects the non-causal reference, the bias arm the bias-free
-    reference and the reference whose table is reversed along k - q (S > 1: a single key has weight 1 whatever its score)."""
+    reference and the reference whose table is reversed along k - q (S > 1: a single key has weight 1 whatever its score);
+    `both` (mask and table at once: no tower uses it, the entry point allows it) rejects the reference without either."""
     ops = _ops()
     w = H * d
     g = _g(B * 1000 + H * 100 + S + d)
@@ -66,8 +72,8 @@ def test_text_attn_fwd(B, H, S, d, arm):
     obuf[:, 1::2] = float("-inf")
     buf0, obuf0 = buf.clone(), obuf.clone()
     scale = d ** -0.5
-    causal = arm == "causal"
-    table = 2.0 * torch.randn(H, 2 * S - 1, device="cuda", generator=g) if arm == "bias" else None
+    causal = arm in ("causal", "both")
+    table = 2.0 * torch.randn(H, 2 * S - 1, device="cuda", generator=g) if arm in ("bias", "both") else None
     assert ops.text_attn_fwd(buf[1, GUARD:], ld, obuf[1, GUARD:], ldo, B, H, S, d, scale, causal=causal, rel_bias=table)
     torch.cuda.synchronize()
     assert torch.equal(buf.view(torch.int16), buf0.view(torch.int16))                    # the operands are only read
@@ -91,6 +97,9 @@ def test_text_attn_fwd(B, H, S, d, arm):
     if S > 1 and arm == "bias":
         assert not A.rows_close(out, T.attention(qb, kb, vb, scale), budget, A.C["O"])[0]
         assert not A.rows_close(out, T.attention(qb, kb, vb, scale, table=table.flip(1)), budget, A.C["O"])[0]
+    if arm == "both":
+        assert not A.rows_close(out, T.attention(qb, kb, vb, scale, False, table), budget, A.C["O"])[0]
+        assert not A.rows_close(out, T.attention(qb, kb, vb, scale, True), budget, A.C["O"])[0]
 
 
 def test_text_attn_fwd_causal_with_a_table_and_refusals():
