@@ -56,8 +56,28 @@ int mgx_flow_step_fwd(const float* x, const uint16_t* v, const uint16_t* noise, 
 int mgx_flow_step_bwd(const float* x, const uint16_t* v, const float* prev, const float* g_logp, uint16_t* dv,
                       int B, long n, const mgx_flow_coeffs* k /*host*/, void* stream);
 
+/* KL penalty of a replayed Flow-GRPO step to a frozen reference policy (trainer flag --kl_ref_coeff; LoRA runs, where
+ * the adapter-free base is the reference).  NOT in the reference trainer, whose --kl_coeff term 0.5 (lp_new - lp_old)^2
+ * is taken to the rollout policy of the same step.  v_ref bf16 [B,n] is the reference policy's model output on the
+ * same inputs and carries no gradient.  With mean(u) = x * c_x + bf16(bf16(u * c_v) * dt_mean), the mean_out of
+ * mgx_flow_step_fwd:
+ *   kl[b] = mean over n of (mean(v) - mean(v_ref))^2 / den          (den = 2 sd^2: the closed-form KL of two
+ *                                                                    Gaussians of equal sd, averaged like logp)
+ * ws as for mgx_flow_step_fwd (mgx_logp_workspace_elems doubles; per-block partials, fixed-order finalize, no
+ * atomics).  Streams 8 bytes per element. */
+int mgx_flow_kl_fwd(const float* x, const uint16_t* v, const uint16_t* v_ref, float* kl_out, double* ws, int B, long n,
+                    const mgx_flow_coeffs* k /*host*/, void* stream);
+
+/* mgx_flow_step_bwd with that term: g_kl fp32 [B] is dLoss/dkl.  Both gradients meet at the fp32 mean, as under
+ * autograd, before the bf16 chain to dv:
+ *   gm = (g_logp / n / den) * 2 (prev - mean(v)) + (g_kl / n / den) * 2 (mean(v) - mean(v_ref))
+ * With g_kl zero or v_ref == v the result is mgx_flow_step_bwd's bit for bit.  14 bytes per element. */
+int mgx_flow_step_kl_bwd(const float* x, const uint16_t* v, const uint16_t* v_ref, const float* prev,
+                         const float* g_logp, const float* g_kl, uint16_t* dv, int B, long n,
+                         const mgx_flow_coeffs* k /*host*/, void* stream);
+
 typedef struct {
-  float ds_r;     /* mean0 = x + bf16(v * ds_r)        sampling_utils.py:224 (scalar rounded to bf16) */
+  float ds_r;    /* mean0 = x + bf16(v * ds_r)        sampling_utils.py:224 (scalar rounded to bf16) */
   float s_r;      /* x0    = x - bf16(v * s_r)         sampling_utils.py:226 */
   float ds;       /* unrounded sigma_next - sigma (score-correction term :234) */
   float ds_b;     /* scalar autograd uses for d(ds*v)/dv (unrounded on CPU semantics) */

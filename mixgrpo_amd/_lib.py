@@ -45,6 +45,8 @@ SIGNATURES = {
     "mgx_logp_workspace_elems": (_L, [_I, _L]),
     "mgx_flow_step_fwd": (_I, [_P] * 9 + [_I, _L, C.POINTER(FlowCoeffs), _I, _P]),
     "mgx_flow_step_bwd": (_I, [_P] * 5 + [_I, _L, C.POINTER(FlowCoeffs), _P]),
+    "mgx_flow_kl_fwd": (_I, [_P] * 5 + [_I, _L, C.POINTER(FlowCoeffs), _P]),
+    "mgx_flow_step_kl_bwd": (_I, [_P] * 7 + [_I, _L, C.POINTER(FlowCoeffs), _P]),
     "mgx_dance_step_fwd": (_I, [_P] * 8 + [_I, _L, C.POINTER(DanceCoeffs), _I, _P]),
     "mgx_dance_step_bwd": (_I, [_P] * 5 + [_I, _L, C.POINTER(DanceCoeffs), _I, _P]),
     "mgx_dpm_step_fwd": (_I, [_P] * 9 + [_I, _L, C.POINTER(DpmCoeffs), _P]),

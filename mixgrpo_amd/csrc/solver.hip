@@ -146,6 +146,57 @@ flow_bwd_kernel(const float* __restrict__ x, const bf16_raw* __restrict__ v, con
   }
 }
 
+// KL of the step's Gaussian to the one a frozen reference policy's output v_ref gives (same x, same sd):
+// mean over n of (mean(v) - mean(v_ref))^2 / den.  Not in the reference ("Low-rank adapters").  8 B / element.
+__global__ void __launch_bounds__(kThreads)
+flow_kl_fwd_kernel(const float* __restrict__ x, const bf16_raw* __restrict__ v, const bf16_raw* __restrict__ v_ref,
+                   double* __restrict__ ws, long n, mgx_flow_coeffs k) {
+  const long base = (long)blockIdx.y * n;
+  float part = 0.f;
+  for (long i = ((long)blockIdx.x * kThreads + threadIdx.x) * kVec; i < n; i += (long)gridDim.x * kThreads * kVec) {
+    const long o = base + i;
+    F8 xv = ld_f32x8(x + o), vv = ld_bf16x8(v + o), rv = ld_bf16x8(v_ref + o);
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      const float xc = xv.v[j] * k.c_x;
+      const float m = xc + rbf(rbf(vv.v[j] * k.c_v) * k.dt_mean);
+      const float mr = xc + rbf(rbf(rv.v[j] * k.c_v) * k.dt_mean);
+      const float d = m - mr;
+      part += (d * d) / k.den;
+    }
+  }
+  const double t = block_sum(part);
+  if (threadIdx.x == 0) ws[(long)blockIdx.y * gridDim.x + blockIdx.x] = t;
+}
+
+// flow_bwd_kernel with the KL term's gradient summed into d loss / d mean(v) -- the fp32 node both consumers of the mean
+// meet at -- before the bf16 chain.  A zero KL gradient leaves gm, and every bit behind it, as flow_bwd_kernel forms it.
+__global__ void __launch_bounds__(kThreads)
+flow_kl_bwd_kernel(const float* __restrict__ x, const bf16_raw* __restrict__ v, const bf16_raw* __restrict__ v_ref,
+                   const float* __restrict__ prev, const float* __restrict__ g_logp, const float* __restrict__ g_kl,
+                   bf16_raw* __restrict__ dv, long n, mgx_flow_coeffs k) {
+  const long base = (long)blockIdx.y * n;
+  const float g = (g_logp[blockIdx.y] / (float)n) / k.den;
+  const float gk = (g_kl[blockIdx.y] / (float)n) / k.den;
+  for (long i = ((long)blockIdx.x * kThreads + threadIdx.x) * kVec; i < n; i += (long)gridDim.x * kThreads * kVec) {
+    const long o = base + i;
+    F8 xv = ld_f32x8(x + o), vv = ld_bf16x8(v + o), rv = ld_bf16x8(v_ref + o), pv = ld_f32x8(prev + o), out;
+#pragma unroll
+    for (int j = 0; j < kVec; ++j) {
+      const float xc = xv.v[j] * k.c_x;
+      const float m = xc + rbf(rbf(vv.v[j] * k.c_v) * k.dt_mean);
+      const float mr = xc + rbf(rbf(rv.v[j] * k.c_v) * k.dt_mean);
+      const float a = g * (2.f * (pv.v[j] - m));     // d logp / d mean, as flow_bwd_kernel
+      const float b = gk * (2.f * (m - mr));         // d kl / d mean
+      const float gm = b == 0.f ? a : a + b;         // (a + 0 would turn a = -0 into +0)
+      const float g2 = rbf(gm);
+      const float g1 = rbf(g2 * k.dt_mean);
+      out.v[j] = g1 * k.c_v;                         // rounded to bf16 by the store
+    }
+    st_bf16x8(dv + o, out);
+  }
+}
+
 // ------------------------------------------------------------------------------------------- dance step
 template <bool REPLAY, bool SDE>
 __global__ void __launch_bounds__(kThreads)
@@ -366,6 +417,29 @@ extern "C" int mgx_flow_step_bwd(const float* x, const uint16_t* v, const float*
   if (int e = check_common(B, n)) return e;
   MGX_REQUIRE(x && v && prev && g_logp && dv && k, "null argument");
   flow_bwd_kernel<<<dim3(blocks_per_sample(n), B), kThreads, 0, (hipStream_t)stream>>>(x, v, prev, g_logp, dv, n, *k);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int mgx_flow_kl_fwd(const float* x, const uint16_t* v, const uint16_t* v_ref, float* kl_out, double* ws, int B,
+                               long n, const mgx_flow_coeffs* k, void* stream) {
+  if (int e = check_common(B, n)) return e;
+  MGX_REQUIRE(x && v && v_ref && kl_out && ws && k, "null argument");
+  const int nb = blocks_per_sample(n);
+  hipStream_t st = (hipStream_t)stream;
+  flow_kl_fwd_kernel<<<dim3(nb, B), kThreads, 0, st>>>(x, v, v_ref, ws, n, *k);
+  logp_finalize_kernel<<<B, kThreads, 0, st>>>(ws, kl_out, nb, n);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int mgx_flow_step_kl_bwd(const float* x, const uint16_t* v, const uint16_t* v_ref, const float* prev,
+                                    const float* g_logp, const float* g_kl, uint16_t* dv, int B, long n,
+                                    const mgx_flow_coeffs* k, void* stream) {
+  if (int e = check_common(B, n)) return e;
+  MGX_REQUIRE(x && v && v_ref && prev && g_logp && g_kl && dv && k, "null argument");
+  flow_kl_bwd_kernel<<<dim3(blocks_per_sample(n), B), kThreads, 0, (hipStream_t)stream>>>(x, v, v_ref, prev, g_logp, g_kl, dv,
+                                                                                          n, *k);
   MGX_CHECK_LAUNCH();
   return MGX_OK;
 }

@@ -14,6 +14,7 @@ the double blocks are row-batched views of it (no concat/split copies).  Paramet
 buffer (+ a bf16 mirror with the identical element order) in which to_q|to_k|to_v are adjacent, so the fused
 QKV projection is a view.
 """
+import contextlib
 import json
 import math
 import os
@@ -235,6 +236,9 @@ class FluxTransformer2DModel(torch.nn.Module):
         self.last_train_route = None              # of the last training forward (FluxFunction): "plain" | "padded_kv"
         self.padded_kv_train_calls = 0
         self.lora = None                          # lora.LoraStore once adapters are attached (add_lora / load_lora)
+        self._reference_active = False            # inside `reference_policy()`
+        self._reference_saved = None              # its side buffer: the merged targets while the base's are in `store.w16`
+        self.last_ref_kl = None                   # the last train step's mean KL to the base policy (--kl_ref_coeff), else None
 
     # ------------------------------------------------------------------ low-rank adapters (lora.py)
     @property
@@ -279,11 +283,49 @@ class FluxTransformer2DModel(torch.nn.Module):
             return self
         self.lora.unmerge(self.store)
         self.lora = None
+        self._reference_saved = None
         del self.lora_param
         for k in ("lora_rank", "lora_alpha", "lora_target_modules"):
             self.config.pop(k, None)
         self.flat_param.requires_grad_(True)
         return self
+
+    @contextlib.contextmanager
+    def reference_policy(self):
+        """Inside: every forward is the adapter-free base policy's -- the targets' compute copy is bf16(W0), bit for bit what
+        `unload_lora()` leaves -- and builds no graph.  It takes the route the policy's own forward would take: the training
+        route's kernels (flux_backward.train_forward; the two routes do not agree in bits) when the model is in training
+        mode with gradients enabled, else the no-grad route, so with B = 0 its output is the policy's bit for bit.
+        Outside: `store.w16` is bit for bit what it was.
+
+        How: the merged targets are saved into a side buffer (2 bytes per target weight, allocated on first use and kept:
+        `reference_policy_bytes`), `LoraStore.unmerge` writes bf16(W0) over them, and the exit copies them back -- a copy,
+        not a second `merge` ("LoRA path").  A training-route pass overwrites the saved activations
+        of a pending backward of the same shape: run it BEFORE the policy's grad-enabled forward."""
+        if self.lora is None:
+            raise MgxError("reference_policy: no adapters attached (the model is its own reference)")
+        if self._reference_active:
+            raise MgxError("reference_policy: already inside one")
+        lo, st = self.lora, self.store
+        views = [st.view(st.w16, f"{module}.weight") for module, _, _ in lo.targets]
+        total = sum(v.numel() for v in views)
+        if self._reference_saved is None or self._reference_saved.numel() != total:
+            self._reference_saved = torch.empty(total, dtype=BF16, device=st.device)
+        saved = torch.split(self._reference_saved, [v.numel() for v in views])
+        flat = [v.view(-1) for v in views]
+        torch._foreach_copy_(list(saved), flat)                   # (one launch per group of tensors, not one per target)
+        lo.unmerge(st)
+        self._reference_active = True
+        try:
+            yield self
+        finally:
+            self._reference_active = False
+            torch._foreach_copy_(flat, list(saved))
+
+    @property
+    def reference_policy_bytes(self):
+        """Device bytes `reference_policy` holds for the saved merged targets (0 before its first use)."""
+        return 0 if self._reference_saved is None else self._reference_saved.numel() * 2
 
     def lora_state_dict(self):
         """{`transformer.<module>.lora_A.weight` [r, K], `transformer.<module>.lora_B.weight` [N, r]}: fp32, the adapter
@@ -641,7 +683,13 @@ class FluxTransformer2DModel(torch.nn.Module):
 
     def forward(self, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections, img_ids,
                 joint_attention_kwargs=None, return_dict=False):
-        if torch.is_grad_enabled() and self.training and self.trainable_param.requires_grad:
+        if self._reference_active and torch.is_grad_enabled() and self.training:
+            from .flux_backward import train_forward
+            with torch.no_grad():                  # the training route's kernels, nothing kept for a backward
+                out = train_forward(self, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections,
+                                    img_ids)[0]
+            return (out,)
+        if torch.is_grad_enabled() and self.training and self.trainable_param.requires_grad and not self._reference_active:
             from .flux_backward import FluxFunction
             out = FluxFunction.apply(self.trainable_param, self, hidden_states, encoder_hidden_states, timestep, guidance,
                                      txt_ids, pooled_projections, img_ids)

@@ -202,47 +202,57 @@ def _train_buffers(cfg, w, device):
     return base.view(w.B)
 
 
+def train_forward(model, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids, pooled_projections, img_ids):
+    """The training route's forward pass: every block into its keep buffers.  Returns (out, w, tr, saved, generation): the
+    output and what a backward needs.  `FluxFunction.forward` is this plus the autograd context; a caller that wants the
+    training route's kernels and no backward (`FluxTransformer2DModel.reference_policy`) drops everything but `out`."""
+    cfg = model.cfg
+    B, N, _ = hidden_states.shape
+    L = encoder_hidden_states.shape[1]
+    # ops.ATTN_PAD_KV: a sequence off 256 runs on the workspace of the next multiple, zero image rows appended, the rows
+    # >= kv_len masked in the attention forward (model._attn) and backward (_attn_bwd); the workspace view of this call
+    # carries kv_len, and serves the backward
+    N_pad = model._pad_kv_rows_train(B, L, N)
+    kv_len = None
+    if N_pad is not None:
+        hidden_states, img_ids = model._padded_inputs(hidden_states, img_ids, N_pad)
+        kv_len = L + N
+    w = model._workspace(B, L, N if N_pad is None else N_pad, kv_len=kv_len)
+    tr = _train_buffers(cfg, w, model.store.device)
+    ehs = model._embed(w, hidden_states, encoder_hidden_states)
+    keep = {}
+    temb, st = model._temb(B, timestep.to(model.store.device), guidance, pooled_projections, keep=keep)
+    cos, sin = model._rope(txt_ids, img_ids)
+    mods = []
+    for blk in range(cfg.num_layers + cfg.num_single_layers):
+        tr.block_in[blk].copy_(w.X)
+        if blk < cfg.num_layers:
+            mods.append(model._double_block(blk, w, st, cos, sin, _BlockPlan(w, True, tr, blk)))
+        else:
+            mods.append(model._single_block(blk - cfg.num_layers, w, st, cos, sin, _BlockPlan(w, False, tr, blk)))
+    tr.x_final.copy_(w.X)
+    out, e = model._head(w, st)
+    model.last_train_route = "plain" if kv_len is None else "padded_kv"
+    model.padded_kv_train_calls += int(kv_len is not None)
+    # the saved activations live in the model's shared per-shape workspace: ONE pending backward per model at a time
+    # (INTEGRATION.md).  A second grad-enabled forward before this one's backward would overwrite them: stamped here,
+    # checked in backward.
+    w.train.generation = getattr(w.train, "generation", 0) + 1
+    saved = dict(ehs=ehs, in16=w.in16.clone(), temb=temb, st=st, keep=keep, cos=cos, sin=sin, mods=mods, e=e)
+    return (out if kv_len is None else out[:, :N].contiguous()), w, tr, saved, w.train.generation
+
+
 class FluxFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flat_param, model, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids,
                 pooled_projections, img_ids):
-        cfg = model.cfg
-        B, N, _ = hidden_states.shape
-        L = encoder_hidden_states.shape[1]
-        # ops.ATTN_PAD_KV: a sequence off 256 runs on the workspace of the next multiple, zero image rows appended, the rows
-        # >= kv_len masked in the attention forward (model._attn) and backward (_attn_bwd); the workspace view of this call
-        # carries kv_len, and serves the backward
-        N_pad = model._pad_kv_rows_train(B, L, N)
-        kv_len = None
-        if N_pad is not None:
-            hidden_states, img_ids = model._padded_inputs(hidden_states, img_ids, N_pad)
-            kv_len = L + N
-        w = model._workspace(B, L, N if N_pad is None else N_pad, kv_len=kv_len)
-        tr = _train_buffers(cfg, w, model.store.device)
-        ehs = model._embed(w, hidden_states, encoder_hidden_states)
-        keep = {}
-        temb, st = model._temb(B, timestep.to(model.store.device), guidance, pooled_projections, keep=keep)
-        cos, sin = model._rope(txt_ids, img_ids)
-        mods = []
-        for blk in range(cfg.num_layers + cfg.num_single_layers):
-            tr.block_in[blk].copy_(w.X)
-            if blk < cfg.num_layers:
-                mods.append(model._double_block(blk, w, st, cos, sin, _BlockPlan(w, True, tr, blk)))
-            else:
-                mods.append(model._single_block(blk - cfg.num_layers, w, st, cos, sin, _BlockPlan(w, False, tr, blk)))
-        tr.x_final.copy_(w.X)
-        out, e = model._head(w, st)
-        model.last_train_route = "plain" if kv_len is None else "padded_kv"
-        model.padded_kv_train_calls += int(kv_len is not None)
-        # the saved activations live in the model's shared per-shape workspace: ONE pending backward per model at a time
-        # (INTEGRATION.md).  A second grad-enabled forward before this one's backward would overwrite them: stamped here,
-        # checked in backward.
-        w.train.generation = getattr(w.train, "generation", 0) + 1
-        ctx.generation = w.train.generation
+        out, w, tr, saved, generation = train_forward(model, hidden_states, encoder_hidden_states, timestep, guidance, txt_ids,
+                                                      pooled_projections, img_ids)
+        ctx.generation = generation
         ctx.model, ctx.w, ctx.tr = model, w, tr
-        ctx.rows = N
-        ctx.saved = dict(ehs=ehs, in16=w.in16.clone(), temb=temb, st=st, keep=keep, cos=cos, sin=sin, mods=mods, e=e)
-        return out if kv_len is None else out[:, :N].contiguous()
+        ctx.rows = hidden_states.shape[1]
+        ctx.saved = saved
+        return out
 
     @staticmethod
     def backward(ctx, dout):

@@ -172,6 +172,56 @@ class _FlowReplayLogp(torch.autograd.Function):
         return dv, None, None, None
 
 
+def flow_kl(x, v, v_ref, k):
+    """kl [B] of `mgx_flow_kl_fwd` for contiguous x fp32 [B, ...], v / v_ref bf16 and one coefficient struct."""
+    B, n = _flat(x)
+    kl = torch.empty(B, dtype=_F32, device=x.device)
+    check(lib().mgx_flow_kl_fwd(ptr(x), ptr(v), ptr(v_ref), ptr(kl), ptr(logp_workspace(B, n, x.device)), B, n, C.byref(k),
+                                stream()))
+    return kl
+
+
+class _FlowReplayLogpKl(torch.autograd.Function):
+    """`_FlowReplayLogp` plus the KL of the step's Gaussian to a frozen reference policy's (`mgx_flow_kl_fwd`); one fused
+    backward for both outputs (`mgx_flow_step_kl_bwd`)."""
+
+    @staticmethod
+    def forward(ctx, model_output, ref_model_output, latents, prev_sample, k):
+        B, n = _flat(latents)
+        v, v_ref = _as(model_output, _BF16), _as(ref_model_output, _BF16)
+        logp = torch.empty(B, dtype=_F32, device=v.device)
+        check(lib().mgx_flow_step_fwd(ptr(latents), ptr(v), None, ptr(prev_sample), None, None, None, ptr(logp),
+                                      ptr(logp_workspace(B, n, v.device)), B, n, C.byref(k), 0, stream()))
+        kl = flow_kl(latents, v, v_ref, k)
+        ctx.save_for_backward(v, v_ref, latents, prev_sample)
+        ctx.k = k
+        return logp, kl
+
+    @staticmethod
+    def backward(ctx, g, g_kl):
+        v, v_ref, latents, prev_sample = ctx.saved_tensors
+        B, n = _flat(latents)
+        dv = torch.empty_like(v)
+        check(lib().mgx_flow_step_kl_bwd(ptr(latents), ptr(v), ptr(v_ref), ptr(prev_sample), ptr(_as(g, _F32)),
+                                         ptr(_as(g_kl, _F32)), ptr(dv), B, n, C.byref(ctx.k), stream()))
+        return dv, None, None, None, None
+
+
+def flow_grpo_step_kl(model_output, ref_model_output, latents, eta, sigmas, index, prev_sample):
+    """The replayed Flow-GRPO step with a KL penalty to a frozen reference policy -> (log_prob fp32 [B], kl fp32 [B]).
+    `ref_model_output` is that policy's output on the same inputs (no gradient).  kl = mean((mean(v) - mean(v_ref))^2 /
+    (2 sd^2)): the KL between the two steps' Gaussians, averaged over elements like the log-prob.  Differentiable in
+    `model_output`.  Not in the reference ("Low-rank adapters"); replay form only: `prev_sample` is required."""
+    if prev_sample is None:
+        raise ValueError("flow_grpo_step_kl replays a stored transition: prev_sample is required")
+    k = flow_coeffs(sigmas, int(index), eta)
+    x, prev = _as(latents, _F32), _as(prev_sample, _F32)
+    if model_output.requires_grad and torch.is_grad_enabled():
+        return _FlowReplayLogpKl.apply(model_output, ref_model_output, x, prev, k)
+    with torch.no_grad():
+        return _FlowReplayLogpKl.apply(model_output.detach(), ref_model_output, x, prev, k)
+
+
 class _DanceReplayLogp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model_output, latents, prev_sample, k, sde):

@@ -39,7 +39,7 @@ def default_args(**kw):
              timestep_fraction=0.6, frozen_init_timesteps=-1, dpm_algorithm_type="null", dpm_apply_strategy="post",
              dpm_post_compress_ratio=0.4, dpm_solver_order=2, dpm_solver_type="midpoint",
              sample_strategy="progressive", output_dir="data/outputs", experiment_name="exp", reward_model="synthetic",
-             rollout_batch=0, train_microbatch=0, skip_dead_backward=False)
+             rollout_batch=0, train_microbatch=0, skip_dead_backward=False, kl_ref_coeff=0.0)
     a.update(kw)
     return Namespace(**a)
 
@@ -188,6 +188,29 @@ def compute_advantages(args, rewards, reward_weights, gathered):
     return adv
 
 
+def is_flow_grpo_replay(args):
+    """True when the replay is the Flow-GRPO step: what `_replay_backward` calls `use_flow and args.flow_grpo_sampling`."""
+    use_flow = args.dpm_algorithm_type == "null" or ("dpmsolver" in args.dpm_algorithm_type and args.dpm_apply_strategy == "post")
+    return bool(use_flow and args.flow_grpo_sampling)
+
+
+def check_ref_kl_args(args, use_lora):
+    """`--kl_ref_coeff` > 0 (the KL penalty to the frozen, adapter-free base policy; not in the reference trainer) needs
+    adapters -- the base is only frozen and on the device under `--use_lora` -- and the Flow-GRPO replay, whose Gaussian
+    step the closed-form KL is written for.  Raises a ValueError naming the flag otherwise.  Needs no model."""
+    coeff = float(getattr(args, "kl_ref_coeff", 0.0) or 0.0)
+    if coeff < 0:
+        raise ValueError(f"--kl_ref_coeff must not be negative (got {coeff})")
+    if coeff == 0:
+        return
+    if not use_lora:
+        raise ValueError("--kl_ref_coeff needs --use_lora: the reference policy is the frozen base under the adapters, and a "
+                         "full fine-tune keeps no second copy of the model")
+    if not is_flow_grpo_replay(args):
+        raise ValueError("--kl_ref_coeff is defined for the Flow-GRPO replay only: --flow_grpo_sampling with "
+                         "--dpm_algorithm_type null, or dpmsolver* with --dpm_apply_strategy post")
+
+
 def _trainable_store(transformer):
     """The flat store gradients live in: the adapters' when LoRA adapters are attached, else the model's parameter store."""
     return getattr(transformer, "trainable_store", None) or getattr(transformer, "store", None)
@@ -297,7 +320,12 @@ def train_one_step(args, device, transformer, vae, reward_function, optimizer, l
     accum = args.gradient_accumulation_steps
     denom = float(accum * nt) if nt > 0 else 1.0
     mb = getattr(args, "train_microbatch", 0) or 0
-    log = torch.zeros(4, device=device, dtype=F32)            # loss, policy, kl, clip_frac sums (device)
+    kl_ref = float(getattr(args, "kl_ref_coeff", 0.0) or 0.0)
+    if kl_ref > 0:
+        check_ref_kl_args(args, getattr(transformer, "lora", None) is not None)
+    # loss, policy, kl, clip_frac sums (device); with --kl_ref_coeff a fifth: the sum of the pairs' KL to the base policy
+    log = torch.zeros(5 if kl_ref > 0 else 4, device=device, dtype=F32)
+    n_replayed = 0
     grad_norm = None
     lat_steps = all_latents.transpose(0, 1)                   # [T'+1, B, N, C] view (step-major storage)
     guidance = torch.tensor([3.5], device=device, dtype=BF16)
@@ -312,6 +340,7 @@ def train_one_step(args, device, transformer, vae, reward_function, optimizer, l
         # `args.skip_dead_backward` only their forward runs (their losses still enter the logged averages): every
         # returned value and the weights are identical, the dead backward passes are not executed.
         dead = len(chunk) < accum and getattr(args, "skip_dead_backward", False)
+        n_replayed += len(pairs)
         if pairs:
             pairs.sort(key=lambda p: p[1])                     # step-major: one coefficient set per contiguous slice
             for m0 in range(0, len(pairs), mb or len(pairs)):
@@ -339,10 +368,16 @@ def train_one_step(args, device, transformer, vae, reward_function, optimizer, l
                 trace.setdefault("grad_norms", []).append(grad_norm.clone())
             lr_scheduler.step()
             optimizer.zero_grad()
-    allreduce_mean_vec_(log)                                   # one collective for the four logging averages
+    if kl_ref > 0:
+        log[4] /= max(n_replayed, 1)                           # the step's mean unweighted KL over the replayed pairs
+    allreduce_mean_vec_(log)                                   # one collective for the logging averages
     if is_dist():
         dist.barrier()
     vals = log.tolist()                                        # the step's single device->host sync
+    if kl_ref > 0:
+        transformer.last_ref_kl = vals[4]
+        if trace is not None:
+            trace["ref_kl"] = vals[4]
     if args.multi_reward_mix == "advantage_aggr":
         rres = {k: v.mean().item() for k, v in gathered.items()}
     else:
@@ -365,10 +400,18 @@ def _replay_backward(args, transformer, pairs, lat_steps, all_log_probs, adv, eh
     old_lp = all_log_probs[idx_s, idx_t].contiguous()
     a = adv[idx_s].contiguous()
     ts = _timestep_tensor([timestep_value[p[1]] for p in pairs], dev)
+    kl_ref = float(getattr(args, "kl_ref_coeff", 0.0) or 0.0)
+    fwd_kw = dict(hidden_states=x, encoder_hidden_states=ehs[idx_s].contiguous(), timestep=ts, guidance=guidance, txt_ids=txt_ids,
+                  pooled_projections=pooled[idx_s].contiguous(), img_ids=img_ids, joint_attention_kwargs=None, return_dict=False)
+    fwd = lambda: transformer(**fwd_kw)[0]
+    v_ref = None
+    if kl_ref > 0:
+        # the frozen base policy on the same inputs, on the route the policy's forward below takes, and BEFORE it: the pass
+        # shares the workspace and the kept activations of the one pending backward
+        with torch.autocast("cuda", torch.bfloat16), torch.set_grad_enabled(need_grad), transformer.reference_policy():
+            v_ref = fwd().detach().contiguous()
     with torch.autocast("cuda", torch.bfloat16), torch.set_grad_enabled(need_grad):
-        pred = transformer(hidden_states=x, encoder_hidden_states=ehs[idx_s].contiguous(), timestep=ts,
-                           guidance=guidance, txt_ids=txt_ids, pooled_projections=pooled[idx_s].contiguous(),
-                           img_ids=img_ids, joint_attention_kwargs=None, return_dict=False)[0]
+        pred = fwd()
     P = len(pairs)
     use_flow = args.dpm_algorithm_type == "null" or ("dpmsolver" in args.dpm_algorithm_type
                                                      and args.dpm_apply_strategy == "post")
@@ -411,6 +454,13 @@ def _replay_backward(args, transformer, pairs, lat_steps, all_log_probs, adv, eh
                                            new_lp[lo:hi].data_ptr(), ptr(SU.logp_workspace(hi - lo, n, dev)), hi - lo, n,
                                            C.byref(kf), 1, stream()))
         coeffs.append(kf)
+    kl = None
+    if kl_ref > 0:
+        kl = torch.empty(P, device=dev, dtype=F32)             # KL of every pair's step to the base policy's
+        for (lo, hi, t), kf in zip(slices, coeffs):
+            check(lib().mgx_flow_kl_fwd(ptr(x[lo:hi]), ptr(v[lo:hi]), ptr(v_ref[lo:hi]), kl[lo:hi].data_ptr(),
+                                        ptr(SU.logp_workspace(hi - lo, n, dev)), hi - lo, n, C.byref(kf), stream()))
+        g_kl = torch.full((P,), kl_ref / denom, device=dev, dtype=F32)      # d loss / d kl: the pair's loss gains kl_ref * kl / denom
     out = torch.empty(5, P, device=dev, dtype=F32)             # loss, policy, kl, clip_frac, g_logp
     check(lib().mgx_grpo_loss(ptr(new_lp), ptr(old_lp), ptr(a), P, float(args.clip_range), float(args.adv_clip_max),
                               float(args.kl_coeff), denom, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
@@ -421,6 +471,10 @@ def _replay_backward(args, transformer, pairs, lat_steps, all_log_probs, adv, eh
             check(lib().mgx_dpm_step_bwd(ptr(x[lo:hi]), ptr(v[lo:hi]), ptr(dpm_xt[lo:hi]), g_lp[lo:hi].data_ptr(),
                                          dv[lo:hi].data_ptr(), hi - lo, n, C.byref(kf),
                                          SU._u(SU._host(sig_host).to(F32)[t]), stream()))
+        elif kl is not None:
+            check(lib().mgx_flow_step_kl_bwd(ptr(x[lo:hi]), ptr(v[lo:hi]), ptr(v_ref[lo:hi]), ptr(nxt[lo:hi]),
+                                             g_lp[lo:hi].data_ptr(), g_kl[lo:hi].data_ptr(), dv[lo:hi].data_ptr(), hi - lo, n,
+                                             C.byref(kf), stream()))
         elif args.flow_grpo_sampling:
             check(lib().mgx_flow_step_bwd(ptr(x[lo:hi]), ptr(v[lo:hi]), ptr(nxt[lo:hi]), g_lp[lo:hi].data_ptr(),
                                           dv[lo:hi].data_ptr(), hi - lo, n, C.byref(kf), stream()))
@@ -429,10 +483,20 @@ def _replay_backward(args, transformer, pairs, lat_steps, all_log_probs, adv, eh
                                            dv[lo:hi].data_ptr(), hi - lo, n, C.byref(kf), 1, stream()))
     if pred.requires_grad:
         pred.backward(dv)
-    log += out[:4].sum(dim=1)
+    if kl is None:
+        log += out[:4].sum(dim=1)
+    else:
+        kl_sum = kl.sum()
+        log[:4] += out[:4].sum(dim=1)
+        log[0] += kl_sum * (kl_ref / denom)
+        log[4] += kl_sum
     if trace is not None:
         trace.setdefault("new_log_probs", []).append((list(pairs), new_lp.clone()))
         trace.setdefault("g_logp", []).append(g_lp.clone())
+        if kl is not None:
+            # the micro-batch's forward arguments and what the fused backward read and wrote: enough to redo either on its own
+            trace.setdefault("ref_kl_replays", []).append(dict(pairs=list(pairs), fwd_kw=fwd_kw, v=v.clone(), v_ref=v_ref, prev=nxt,
+                                                               g_logp=g_lp.clone(), g_kl=g_kl, kl=kl.clone(), dv=dv.clone()))
 
 
 # ------------------------------------------------------------------------------------------------ entry point
@@ -482,6 +546,10 @@ _SWITCHES = ("precondition_outputs", "gradient_checkpointing", "allow_tf32", "us
 # engine options the reference has no flag for (all optional)
 _ENGINE_FLAGS = (("rollout_batch", int, 0), ("train_microbatch", int, 0), ("attention_dtype", str, "bf16"),
                  ("mgx_max_epochs", int, None),
+                 # KL penalty of every replayed Flow-GRPO step to the frozen base policy under the adapters (--use_lora only; not
+                 # in the reference, whose --kl_coeff is taken to the rollout policy of the same step): the pair's loss gains
+                 # kl_ref_coeff * mean((mean(v) - mean(v_ref))^2 / (2 sd^2)) / denom.  One more forward per replayed pair.
+                 ("kl_ref_coeff", float, 0.0),
                  # low-rank adapter fine-tuning (lora.py): frozen base, rank-r adapters on the target modules (comma list of
                  # diffusers module names; default: the eight attention projections), adapter checkpoints
                  ("lora_rank", int, 16), ("lora_alpha", float, None), ("lora_target_modules", str, None),
@@ -601,6 +669,7 @@ def main(args, reward_function=None, reward_weights=None, reward_models=None):
     use_lora = bool(getattr(args, "use_lora", False)) or resume_lora
     if use_lora:
         parse_target_modules(args.lora_target_modules)           # an unsupported name fails here, before any weight is read
+    check_ref_kl_args(args, use_lora)                            # likewise --kl_ref_coeff without adapters / off the Flow-GRPO step
     model_path = args.pretrained_model_name_or_path if resume_lora else \
         (args.resume_from_checkpoint or args.pretrained_model_name_or_path)
     main_print(f"--> loading model from {model_path}")
@@ -716,6 +785,8 @@ def main(args, reward_function=None, reward_weights=None, reward_models=None):
                        "cur_iter_in_group": grpo_states.cur_iter_in_group if grpo_states else 0,
                        "learning_rate": lr_scheduler.get_last_lr()[0], "step_time": step_time,
                        "avg_step_time": sum(step_times) / len(step_times)}
+                if getattr(args, "kl_ref_coeff", 0.0) > 0:
+                    log["ref_kl"] = transformer.last_ref_kl
                 if args.multi_reward_mix == "advantage_aggr" and isinstance(reward, dict):
                     for name, val in reward.items():
                         log[f"reward_{name}"] = val
